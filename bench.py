@@ -12,7 +12,13 @@ global input stream (mbls_g1_msm_jacobian), the Jacobian partials are exchanged 
 all_gather over xGMI, added on the device and normalised once (the reference has
 no multi-GPU path).  value = MSMs of 2^msm_log points completed per second over all GPUs
 (weak scaling), from the median of the K per-step hipEvent times (the max
-over ranks), with mean / min / max and the wall-clock rate of the same K steps in `msm_step_ms`.  The other BASELINE configs are legs of the same run (see `configs` below):
+over ranks), with mean / min / max and the wall-clock rate of the same K steps in `msm_step_ms`.
+
+A plain run does only that: set up, W warmup steps, the K timed steps, the result line.  With
+`--dump-outputs DIR` it also writes what the last timed step computed (see dump_outputs).  `--full`
+adds everything else to the same line: the stage profile and the rooflines, the NTT 2^ntt_log rate
+(the metric's second half), the MSM variants, the CPU baseline, and the other BASELINE configs as
+legs of the same run (see `configs` below):
 #1 vecops (GPU and the CPU path), #2 NTT 2^20 round trip, #4 the 2^24 MSM split over the N
 ranks (strong scaling, digest comparable across N), #5 G2 MSM 2^20 + 4 x NTT 2^22 on two
 streams.  Inputs are synthetic: seeded scalars and bases P_i = k_i G generated on the device.
@@ -137,16 +143,38 @@ def parse():
     ap.add_argument("--no-mix", action="store_true", help="skip the G2 MSM + batched NTT overlap leg (config #5)")
     ap.add_argument("--mix-batch", type=int, default=4, help="NTT polynomials in the config #5 batch")
     ap.add_argument("--msm-batch", type=int, default=8, help="members of the batched-MSM leg (0: skip)")
-    ap.add_argument("--headline-only", action="store_true", help="headline MSM + NTT loops only (profiling)")
+    ap.add_argument("--headline-only", action="store_true",
+                    help="with --full: headline MSM + NTT loops only (profiling)")
     ap.add_argument("--no-stage-profile", action="store_true",
                     help="skip the stage-profiler passes (their hipEvent markers add ~10 us before each stage "
                          "in a kernel trace; use for timelines)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the line can hold: stage profile and "
+                         "rooflines, NTT, MSM variants, configs #1 #2 #4 #5, the CPU baseline (the --no-* options "
+                         "above trim it); without it only the headline MSM steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def digest(t):
     import numpy as np
     return hashlib.sha256(t.detach().cpu().numpy().view(np.uint64).tobytes()).hexdigest()[:16]
+
+
+def dump_outputs(path, result):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float64 .npy.
+    The headline step leaves one G1 point in ICICLE form on the device, (x, y, 1) as 3 x 6
+    little-endian u64 limbs (at N > 1 the same sum on every rank; rank 0 writes).  float64 cannot
+    hold a u64 limb, so g1_msm_result.npy holds its 36 32-bit words, low word first, each exact.
+    The inputs are seeded: equal arguments give equal files from any two builds."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    words = result.detach().cpu().contiguous().numpy().view(np.uint32)
+    np.save(os.path.join(path, "g1_msm_result.npy"), words.astype(np.float64))
 
 
 def free_port():
@@ -297,11 +325,15 @@ def main():
                   "wall_msm_per_sec": round(world * args.steps / msm_time, 3),
                   "n": args.steps, "source": "hipEvents on the MSM stream, max over ranks of each statistic"}
     headline_result = result.clone()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, headline_result)
 
+    # everything below the timed steps is --full's; legs: all of it but the MSM / NTT loops
+    legs_on = args.full and not args.headline_only
     # live per-stage timing (HIP events recorded on the MSM's own stream) for the roofline; the
     # timed steps above run without these events (each marker delays the next dispatch ~10 us)
     msm_prof = {}
-    if not args.no_stage_profile:
+    if args.full and not args.no_stage_profile:
         amd.profile(True)
         for _ in range(max(3, args.steps // 2)):
             msm_step()
@@ -310,11 +342,11 @@ def main():
         amd.profile(False)
 
     extra = {}
-    if not args.headline_only:
+    if legs_on:
         extra.update(msm_variants(args, amd, torch, dev, stream, scalars, bases, n, timed, max_over_ranks, world))
     # ------------------------------------------------------------------ config #4: 2^total split over ranks
     cfg4, cfg4_result = None, None
-    if args.msm_total_log and not args.headline_only:
+    if args.msm_total_log and legs_on:
         total = 1 << args.msm_total_log
         lo, hi = sharded_msm.shard_range(total, world, rank)
         m = hi - lo
@@ -337,25 +369,26 @@ def main():
         torch.cuda.empty_cache()
 
     # ------------------------------------------------------------------ NTT 2^ntt_log (replicas)
-    amd.ntt_init_domain()
     nn = 1 << args.ntt_log
-    x = torch.zeros((nn, 4), dtype=torch.int64, device=dev)
-    y = torch.zeros_like(x)
-    amd.gen_scalars(x, 0x5EED0025, montgomery=True, stream=stream)
-    ntt_ms_wall = max_over_ranks(timed(lambda: amd.ntt(x, out=y, stream=stream, is_async=True), args.steps,
-                                       warm=args.warmup, sync_all=True))
-    ntt_per_sec = world * 1e3 / ntt_ms_wall
-    ntt_prof = {}
-    if not args.no_stage_profile:
-        amd.profile(True)
-        for _ in range(max(3, args.steps // 2)):
-            amd.ntt(x, out=y, stream=stream, is_async=True)
-        torch.cuda.synchronize(dev)
-        ntt_prof = amd.profile_read()
-        amd.profile(False)
+    ntt_per_sec, ntt_prof = None, {}
+    if args.full:
+        amd.ntt_init_domain()
+        x = torch.zeros((nn, 4), dtype=torch.int64, device=dev)
+        y = torch.zeros_like(x)
+        amd.gen_scalars(x, 0x5EED0025, montgomery=True, stream=stream)
+        ntt_ms_wall = max_over_ranks(timed(lambda: amd.ntt(x, out=y, stream=stream, is_async=True), args.steps,
+                                           warm=args.warmup, sync_all=True))
+        ntt_per_sec = world * 1e3 / ntt_ms_wall
+        if not args.no_stage_profile:
+            amd.profile(True)
+            for _ in range(max(3, args.steps // 2)):
+                amd.ntt(x, out=y, stream=stream, is_async=True)
+            torch.cuda.synchronize(dev)
+            ntt_prof = amd.profile_read()
+            amd.profile(False)
 
     legs = {}
-    if not args.headline_only:
+    if legs_on:
         # config #2: NTT 2^20 forward + inverse round trip, device-resident
         x20 = x[: 1 << 20]
         y20 = torch.zeros_like(x20)
@@ -374,10 +407,11 @@ def main():
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N=1)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and not args.headline_only:
+    if rank == 0 and world == 1 and not args.no_cpu and legs_on:
         cpu = cpu_baseline(args, amd, torch, scalars, bases, n, headline_result, x, cfg4_result)
 
-    if rank == 0:
+    def full_fields():
+        """--full's part of the line (rank 0): stage times, rooflines, NTT, config #4, CPU baseline"""
         def avg(prof, key):
             ms, cnt = prof.get(key, (0.0, 0))
             return ms / cnt if cnt else None
@@ -407,27 +441,7 @@ def main():
                   for k in ("k_ntt_pass<true, false, false>", "k_ntt_pass<false, false, false>",
                             "k_ntt_pass<false, true, false>")]
         ntt_issue_ms = round(sum(passes), 4) if args.ntt_log == 22 and all(p is not None for p in passes) else None
-        out = {
-            "metric": "G1 MSM/sec at 2^20 points + Fr NTT/sec at 2^22 (bit-exact vs BLST)",
-            "value": round(msm_per_sec, 3),
-            "unit": "MSM/s",
-            "n_gpus": world,
-            "world_size": dist_world,
-            "rank_devices": ranks_devices,
-            "same_device_rehearsal": same_dev and world > 1,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32-limb Montgomery (Fq 381-bit / Fr 255-bit integer)",
-            "data": "synthetic: seeded scalars, bases k_i*G generated on device",
-            "config": {"workload": f"G1 MSM 2^{args.msm_log} points per GPU, production path (ICICLE entry, "
-                                   f"Montgomery scalars + bases in HBM, (x,y,1) result on device); N>1: "
-                                   f"sharded, RCCL all-gather of partial sums",
-                       "msm_points_per_gpu": n, "ntt_size": nn, "parallelism": f"msm-shard{world}"},
-            "msm_step_ms": step_stats,
+        return {
             "bit_exact": cpu.get("bit_exact") if cpu else None,
             "ntt_per_sec": round(ntt_per_sec, 3),
             "ntt_ms": round(ntt_ms, 4) if ntt_ms else None,
@@ -473,8 +487,35 @@ def main():
             "config4_msm_sharded": cfg4,
             "cpu_baseline": cpu,
         }
-        out.update(extra)
-        out.update(legs)
+
+    if rank == 0:
+        out = {
+            "metric": "G1 MSM/sec at 2^20 points + Fr NTT/sec at 2^22 (bit-exact vs BLST)",
+            "value": round(msm_per_sec, 3),
+            "unit": "MSM/s",
+            "n_gpus": world,
+            "world_size": dist_world,
+            "rank_devices": ranks_devices,
+            "same_device_rehearsal": same_dev and world > 1,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u32-limb Montgomery (Fq 381-bit / Fr 255-bit integer)",
+            "data": "synthetic: seeded scalars, bases k_i*G generated on device",
+            "config": {"workload": f"G1 MSM 2^{args.msm_log} points per GPU, production path (ICICLE entry, "
+                                   f"Montgomery scalars + bases in HBM, (x,y,1) result on device); N>1: "
+                                   f"sharded, RCCL all-gather of partial sums",
+                       "msm_points_per_gpu": n, "ntt_size": nn, "parallelism": f"msm-shard{world}"},
+            "msm_step_ms": step_stats,
+            "full": args.full,
+        }
+        if args.full:
+            out.update(full_fields())
+            out.update(extra)
+            out.update(legs)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

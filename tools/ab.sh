@@ -8,7 +8,7 @@ for A in "$@"; do
   i=$((i+1))
   L=${A%% *}; E=""; [ "$L" != "$A" ] && E=${A#* }
   echo "== $A"
-  env $E MBLS_LIB=$R/midnight-bls12-381-cuda_amd/$L timeout -k 10 240 python bench.py --no-cpu --no-mix --steps 10 \
+  env $E MBLS_LIB=$R/midnight-bls12-381-cuda_amd/$L timeout -k 10 240 python bench.py --full --no-cpu --no-mix --steps 10 \
     > gpurun_out/ab/$i.json 2> gpurun_out/ab/$i.err || exit $?
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(d['value'], d['ntt_per_sec'], d['msm_stage_ms'])" gpurun_out/ab/$i.json
 done

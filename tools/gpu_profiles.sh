@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round profile set (-> gpurun_out/prof_set, copied to profiles/rNN):
-#  1. rocprofv3 --kernel-trace --stats of the headline workload alone (bench.py --headline-only);
+#  1. rocprofv3 --kernel-trace --stats of the headline workload alone (bench.py --full --headline-only);
 #  2. the same for the G2 MSM 2^20 alone (config #5's MSM: tools/stage_probe.py --group g2);
 #  3. PMC passes, one rocprofv3 --pmc run per counter group (no tracing domains with --pmc), over
 #     tools/pmc_probe.py (the bench's 2^20 G1 MSM, 2^20 G2 MSM and 2^22 NTT calls, nothing else):
@@ -13,7 +13,7 @@ O=$R/gpurun_out/prof_set
 rm -rf $O && mkdir -p $O/pmc
 cd /tmp || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- \
-  python3 $R/bench.py --headline-only --no-stage-profile --steps 10 --warmup 2 > $O/headline_bench.json 2> $O/headline_bench.err || exit 1
+  python3 $R/bench.py --full --headline-only --no-stage-profile --steps 10 --warmup 2 > $O/headline_bench.json 2> $O/headline_bench.err || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace_g2 -o run --output-format csv -- \
   python3 $R/tools/stage_probe.py --group g2 --log 20 --reps 5 > $O/g2_stages.json 2> $O/g2_stages.err || exit 1
 i=0
@@ -26,7 +26,7 @@ for P in "SQ_INSTS_VALU SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_SALU SQ
 done
 cd $R || exit 1
 KS=$(find $O/trace -name "*kernel_stats.csv") && python3 tools/prof_summary.py $KS \
-  "headline only: bench.py --headline-only --steps 10 --warmup 2 (setup kernels k_gen_* included)" > $O/headline_kernel_stats.md
+  "headline only: bench.py --full --headline-only --steps 10 --warmup 2 (setup kernels k_gen_* included)" > $O/headline_kernel_stats.md
 cp $KS $O/headline_kernel_stats.csv
 KS2=$(find $O/trace_g2 -name "*kernel_stats.csv") && python3 tools/prof_summary.py $KS2 \
   "G2 MSM 2^20 alone: tools/stage_probe.py --group g2 --log 20 --reps 5 (+2 warmup; setup kernels included)" > $O/g2_kernel_stats.md
