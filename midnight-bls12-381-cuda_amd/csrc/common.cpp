@@ -195,10 +195,6 @@ CtxLease::~CtxLease() {
     P.cv.notify_one();
 }
 
-#ifndef MBLS_SIDE_PRIO
-#define MBLS_SIDE_PRIO 1  // variant builds: 0 = side streams at the lowest priority
-#endif
-
 eIcicleError StreamCtx::ensure_side(size_t nevents, size_t nsides) {
     while (sides.size() < nsides) {
         hipStream_t s;
@@ -206,7 +202,7 @@ eIcicleError StreamCtx::ensure_side(size_t nevents, size_t nsides) {
         // behind the main stream's accumulation workgroups
         int least = 0, greatest = 0;
         MBLS_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        MBLS_TRY(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, MBLS_SIDE_PRIO ? greatest : least));
+        MBLS_TRY(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, greatest));
         sides.push_back(s);
         hipEvent_t j;
         MBLS_TRY(hipEventCreateWithFlags(&j, hipEventDisableTiming));

@@ -28,11 +28,6 @@ static int optimal_c(long long n) {
 
 int precompute_shift(int F) { return F > 1 ? (256 + F - 1) / F : 0; }
 
-// -DMBLS_PART_SORT=0 (variant builds) forces the tiled digits + scatter sort for every c; the
-// shipped library uses it for c > 16 only
-#ifndef MBLS_PART_SORT
-#define MBLS_PART_SORT 1
-#endif
 #ifndef SLOT0_MIN_TABLE_BYTES
 #define SLOT0_MIN_TABLE_BYTES (1ull << 30)  // G1 shift tables above run the GLV plan on slot 0 (shift_plan)
 #endif
@@ -93,7 +88,6 @@ static int auto_c(long long n, int split, int F, int endo) {
 // on slot 0 of the table (plan.bstride = F): P_i is the table's entry i F, and the split kernel
 // writes a compact per-call [P, phi P] / [P, psi P, psi^2 P, psi^3 P].
 static bool shift_plan(long long n, int F, int endo) {
-    if (!MBLS_PART_SORT) return true;  // variant builds: no slot-0 plan without the fused front
     if (endo == 2) return (F == 4 || F == 8 || F == 16) && (size_t)n * F * 96 <= SLOT0_MIN_TABLE_BYTES;
     return F == 8 || F == 16;
 }
@@ -149,8 +143,7 @@ eIcicleError make_plan(long long n, const MSMConfig* cfg, MsmPlan& p, int endo) 
         p.sF = precompute_shift(F);
         Wg = (p.sF + c - 1) / c;
         // automatic c: windows balanced inside the block when its top window would be nearly
-        // empty (-DMBLS_PART_SORT=0 variant builds, where every factor runs the shift plan:
-        // F = 3: sF = 86, c 16 -> 15; F = 5: 52, 16 -> 13; F = 7: 37, 16 -> 13)
+        // empty (shift_c's choices never are; a -DMBLS_C=14 build at sF = 64: 14 -> 13)
         if (cfg->c <= 0 && p.sF - c * (Wg - 1) < c - 2) {
             c = (p.sF + Wg - 1) / Wg;
             Wg = (p.sF + c - 1) / c;
@@ -220,7 +213,7 @@ namespace mbls {
 #ifndef MBLS_SEGL_LOG
 #define MBLS_SEGL_LOG MBLS_SEG0_LOG
 #endif
-// the same three for G2: two more lane levels of 2-input segments (the FIPS pair chain) from 8192
+// the same three for G2: two more lane levels of 2-input segments (pair XYZZ chains on raw records) from 8192
 // chains instead of wave-layout levels -- G2 2^20 9.36 / 9.37 -> 9.23 / 9.16 ms
 // (profiles/r06/ab/g2_lane_levels_ab.txt; G1 within 1%, lane_levels_ab.txt)
 #ifndef MBLS_LANE_LEVELS_G2
@@ -577,13 +570,8 @@ __global__ __launch_bounds__(256) void k_copy_pinned(uint4* __restrict__ dst, co
     for (; i < n16; i += stride) dst[i] = src[i];
 }
 
-#ifndef MBLS_PINNED_KERNEL
-#define MBLS_PINNED_KERNEL 1  // variant builds: 0 = hipMemcpyAsync for pinned memory too
-#endif
 eIcicleError stage_to_device(void* dst, const void* src, size_t bytes, hipStream_t st) {
-    const void* alias = (MBLS_PINNED_KERNEL && bytes % 16 == 0 && ((uintptr_t)src & 15) == 0)
-                            ? pinned_host_device_pointer(src)
-                            : nullptr;
+    const void* alias = (bytes % 16 == 0 && ((uintptr_t)src & 15) == 0) ? pinned_host_device_pointer(src) : nullptr;
     if (alias) {
         const size_t n16 = bytes / 16;
         size_t blocks = (n16 + 4 * 256 - 1) / (4 * 256);
@@ -1193,7 +1181,7 @@ static int part_fine_bits(uint32_t B) {
     return lb > 8 ? lb - 8 : 0;
 }
 
-bool partition_sort(const MsmPlan& P) { return MBLS_PART_SORT && P.B <= DT_MAX_B; }
+bool partition_sort(const MsmPlan& P) { return P.B <= DT_MAX_B; }
 
 PartSortSizes part_sort_sizes(const MsmPlan& P) {
     PartSortSizes s;
@@ -1389,12 +1377,8 @@ static constexpr uint32_t PS_STAGE = MBLS_PS_STAGE;
 static_assert(PS_STAGE * 4 + (2 * 128 + 1) * 4 <= LDS_LIMIT_BYTES, "MBLS_PS_STAGE too large for the workgroup LDS");
 
 // register-kept entries of the partition sort (k_part_sort): segments per team, entries per lane
-// and segment; MBLS_PS_KEEP=0 builds without it (A/B)
+// and segment
 static constexpr uint32_t PS_RS = 8, PS_RK = 6;
-#ifndef MBLS_PS_KEEP
-#define MBLS_PS_KEEP 1
-#endif
-static constexpr bool PS_KEEP = MBLS_PS_KEEP != 0;
 
 // rank of this lane's entry in LDS counter cnt[key]: the lanes sharing the key of the first
 // remaining lane take one atomic together (up to PEEL such keys per call), the rest one atomic
@@ -1486,10 +1470,7 @@ static_assert(PS_THREADS % 64 == 0 && PS_THREADS <= 1024 && PS_THREADS >= 256, "
 // takes a heavy part's fine counts as the sum of its helpers' (its own workgroup: offsets, counts,
 // chunk counts, no walk), and its PH_HELPERS extra workgroups place their ranges: part base +
 // fine prefix + the earlier helpers' counts of the key + LDS rank.  Without a heavy part (random
-// scalars) every helper exits after the plan.  MBLS_PS_HELP=0 builds without them (A/B).
-#ifndef MBLS_PS_HELP
-#define MBLS_PS_HELP 1
-#endif
+// scalars) every helper exits after the plan.
 static constexpr uint32_t PH_MIN = 32768, PH_QMIN = 8192;
 
 // fn(p, first, H) for every part p < M in order per thread (H = 0: light); all PS_THREADS threads
@@ -1660,10 +1641,10 @@ __global__ __launch_bounds__(PS_THREADS) void k_part_sort(const uint32_t* __rest
     __syncthreads();
     // a team owning <= PS_RS segments of <= PS_RK * PS_TEAM entries each (G1 2^20: 8 of ~64) keeps
     // its lanes' packed entries in registers between the passes, so the placement pass reads no
-    // global memory (MBLS_PS_KEEP=0: both passes walk `ent`); the decision is per team
+    // global memory (otherwise both passes walk `ent`); the decision is per team
     const uint32_t nseg = team < S ? (S - team + nteams - 1) / nteams : 0u;
     uint32_t sk[PS_RS], so[PS_RS], e[PS_RS * PS_RK];
-    bool keep = !help && PACK && PS_KEEP && nseg <= PS_RS;
+    bool keep = !help && PACK && nseg <= PS_RS;
     if (keep) {
 #pragma unroll
         for (uint32_t j = 0; j < PS_RS; ++j) {
@@ -1863,7 +1844,7 @@ eIcicleError launch_part_sort(const MsmPlan& P, const uint32_t* ent, const uint3
     const PartSortSizes z = part_sort_sizes(P);
     if (cc.nchunks && z.FB != CHUNK_FUSED_SHIFT) return MBLS_INVALID_ARGUMENT;
     if (z.FB > 7) return MBLS_INVALID_ARGUMENT;  // 128 fine counters per part (cnt, pre, hh rows)
-    const bool help = MBLS_PS_HELP && hp_in.help && hp_in.hh && hp_in.hpart;
+    const bool help = hp_in.help && hp_in.hh && hp_in.hpart;
     const PartHelp hp = help ? hp_in : PartHelp();
     const uint32_t M = (uint32_t)P.Wg * z.NP;
     dim3 g(M + (help ? PH_HELPERS : 0u)), b(PS_THREADS);

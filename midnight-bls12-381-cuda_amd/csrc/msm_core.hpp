@@ -6,22 +6,27 @@
 // boundary msm_cuda_impl / msm_g2_cuda_impl (icicle_curve_api.cu:243-618).
 //
 // Pipeline (all on the caller's stream, scratch from the per-stream arena):
-//   1. k_digits       (msm_common.hip) one thread per scalar: Montgomery -> standard if
-//                     flagged, signed c-bit digits, (key, index|sign) pairs window-major,
-//                     bucket histogram by atomics.
-//   2. scans          bucket offsets; buckets are split in chunks of <= CHUNK points so one
-//                     heavy bucket (e.g. all-equal scalars) cannot serialise a thread.
-//   3. k_scatter      counting-sort scatter (keys < TB: no radix sort needed).
-//      c <= 16 (default): steps 1-3 are the partitioned counting sort instead
-//                     (k_digits_part + k_part_sort, msm_common.hip 2b).
-//   4. k_accumulate   one thread per chunk: sum of +-P_i by mixed additions -> partial.
-//   5. k_bucket_sum   one thread per bucket: sum of its chunk partials.
-//   6. bucket reduction sum_d d*B_d per window as a recursive running sum (k_reduce_scaled):
-//                     level l splits its inputs in segments of 2^s; each segment's chain walks
-//                     R += V_t, S += R, S += U_t and outputs U' = S and V' = 2^s R, so every level's
-//                     outputs carry weight 1 and the last level's output IS the window sum (no
-//                     scalar multiplications, no per-level tree sums, no window Horner).
-//   7. k_final*       fold over windows: sum_w 2^(c w) G_w (+ ICICLE normalisation).
+//   1-3. sort (msm_common.hip): signed c-bit digits of each scalar (Montgomery -> standard if
+//                     flagged, endomorphism split), contributions (index|sign) sorted by bucket.
+//                     c <= 16 (default): the partitioned counting sort, k_digits_part +
+//                     k_part_sort.  c > 16: k_digits (key, value pairs, bucket histogram by
+//                     atomics), scans, k_scatter.  Then k_chunk_counts / k_chunk_owner: buckets
+//                     are split in chunks of <= P.chunk points so one heavy bucket (e.g.
+//                     all-equal scalars) cannot serialise a thread.
+//   4. k_accumulate_r28 (G1) / k_accumulate_r28p (G2): one thread (lane pair) per chunk, sum of
+//                     +-P_i by mixed additions in radix-2^28 XYZZ -> raw XYZZ partial.
+//   5. k_bucket_small one thread (lane pair) per light bucket: sum of its chunk partials; heavy
+//                     buckets (> SMALL_MAX partials) by slice workgroups of the same launch
+//                     (heavy_slices).  Raw XYZZ bucket sums when level 0 runs in lanes.
+//   6. bucket reduction sum_d d*B_d per window as a recursive running sum: level l splits its
+//                     inputs in segments of 2^s; each segment's chain walks R += V_t, S += R,
+//                     S += U_t and outputs U' = S and V' = 2^s R, so every level's outputs carry
+//                     weight 1 and the last level's output IS the window sum (no scalar
+//                     multiplications, no per-level tree sums, no window Horner).  Lane levels
+//                     over raw XYZZ records: k_reduce_scaled_r28x (G1) / _r28px (G2); row and
+//                     wave levels: k_reduce_scaled<F, MODE>, narrow ones k_reduce_tree4.
+//   7. k_final        fold over windows: sum_w 2^(c w) G_w; k_final_icicle adds ICICLE's
+//                     (x, y, 1) normalisation in the same launch.
 // Precompute factor F (bases table = F blocks of n bases, block f = 2^(c*Wg*f) * P) folds
 // the W windows into Wg = ceil(W/F) groups so the final fold shrinks to (Wg-1)*c doublings.
 #pragma once
@@ -199,170 +204,32 @@ eIcicleError launch_part_sort(const MsmPlan& P, const uint32_t* ent, const uint3
 //    / 8) -- 16 at 2^20 (one 64-byte line of sorted indices per thread, ~5 partials per
 //    bucket), growing with the buckets at 2^22+ so they stay off the heavy-bucket passes
 //    (MBLS_ACC_CHUNK=auto: one round of resident waves, measured slower at 2^20).
+//    G1 (k_accumulate_r28) works in unsaturated radix 2^28 (mbls_fq28.hpp; round 5): the lane
+//    arithmetic runs on 14 x 28-bit limbs, where a column of a product is one v_mad_u64_u32 chain
+//    with no carry tracking (the 32-bit FIPS product pays a v_addc per mad, and on gfx950 every
+//    VALU instruction costs the same ~4 cycles: tools/valu_ceiling.hip).  Points are unpacked 8
+//    bits low (x R 2^8 = x R', free).  The chunk's first point is free, its second an affine +
+//    affine addition (xmmadd), and the next point is staged in LDS by LDS-DMA.  The radix-2^28
+//    field values equal the word arithmetic's (tools/fq28_bench.hip; the GPU parity suite).
 // ------------------------------------------------------------------------------------
-#ifndef MBLS_ACC_MMADD
-#define MBLS_ACC_MMADD 1
-#endif
-#ifndef MBLS_ACC_LDS
-#define MBLS_ACC_LDS 1  // G1: next point prefetched into LDS (LDS-DMA) instead of VGPRs
-#endif
-template <class F, int MINW>
-__global__ __launch_bounds__(256, MINW) void k_accumulate(const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offsets,
-                                                    const uint32_t* __restrict__ chunk_off,
-                                                    const uint32_t* __restrict__ first, uint32_t b0, uint32_t b1,
-                                                    const uint8_t* __restrict__ bases, const uint8_t* __restrict__ phi,
-                                                    uint32_t nsplit, uint32_t chunk, uint8_t* __restrict__ partials) {
-    using L = typename LaneOf<F>::type;
-    // buckets [b0, b1) only (one window group): sorted positions [offsets[b0], offsets[b1]); a
-    // chunk straddling the group boundary is shared, each side summing its own positions
-    const uint32_t gb = offsets[b0], ge = offsets[b1];
-    const uint32_t t = (blockIdx.x * blockDim.x + threadIdx.x) / LaneOf<F>::LANES + gb / chunk;  // chunk index
-    uint32_t beg = t * chunk;
-    const uint32_t end = min(beg + chunk, ge);
-    beg = max(beg, gb);
-    if (beg >= end) return;
-    uint32_t b = first[t];
-    while (offsets[b + 1] <= beg) ++b;  // straddling chunk: the group's first non-empty bucket
-    uint32_t seg = chunk_off[b] + (t - offsets[b] / chunk);
-    uint32_t bend = offsets[b + 1];
-    Jacobian<L> acc = Jacobian<L>::inf();
-    // endomorphism split: indices >= nsplit address the image table (phi(P) / psi^j(P))
-    auto fetch = [&](uint32_t v) {
-        uint32_t idx = v >> 1;
-        const uint8_t* src = idx >= nsplit ? phi : bases;
-        idx = idx >= nsplit ? idx - nsplit : idx;
-        return load_affine<L>(src, idx);
-    };
-    // second point of the chunk (the same step for every lane of the wave): the accumulator is
-    // still the first point, Z = 1, so the affine + affine formula applies (~55% of a mixed
-    // addition); a bucket boundary at this step left it at the identity instead
-    auto step = [&](uint32_t e, const Affine<L>& q) {
-        if (e == bend) {  // bucket boundary inside the chunk: flush, move to the next bucket
-            store_jac<L>(partials, seg, acc);
-            acc = Jacobian<L>::inf();
-            do {
-                ++b;
-            } while (offsets[b + 1] == e);  // skip empty buckets
-            seg = chunk_off[b];
-            bend = offsets[b + 1];
-        }
-        bool done = false;
-        if (MBLS_ACC_MMADD && e == beg + 1 && !acc.is_inf() && !q.is_inf()) done = jac_mmadd(acc, q, acc);
-        if (!done) acc = jac_madd(acc, q);
-    };
-    uint32_t v = sorted[beg];
-    if constexpr (std::is_same<L, Fq>::value && MBLS_ACC_LDS) {
-        // G1: the next point is prefetched into LDS by LDS-DMA (global_load_lds_dwordx4: six
-        // 16-byte pieces per lane, no VGPR destination), double-buffered per wave, instead of
-        // into 24 VGPRs held across the mixed addition: the accumulation fits its 168-VGPR /
-        // 3-waves-per-SIMD bound without spills.  Stage: [slot][wave][piece][lane] x 16 B.
-        __shared__ uint4 stage[2][256 / 64][6][64];
-        const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
-        auto issue = [&](uint32_t vv, uint32_t slot) {
-            uint32_t idx = vv >> 1;
-            const uint8_t* src = idx >= nsplit ? phi : bases;
-            idx = idx >= nsplit ? idx - nsplit : idx;
-            const uint8_t* g = src + (size_t)idx * 96;
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) const void*)(g + 16 * k),
-                                                 (__attribute__((address_space(3))) void*)&stage[slot][wv][k][0], 16, 0, 0);
-        };
-        issue(v, 0);
-        uint32_t vn = beg + 1 < end ? sorted[beg + 1] : v;
-        for (uint32_t e = beg; e < end; ++e) {
-            const uint32_t slot = (e - beg) & 1;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this point's pieces have landed
-            Affine<Fq> p;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const uint4 xa = stage[slot][wv][k][ln], ya = stage[slot][wv][3 + k][ln];
-                p.x.v[4 * k] = xa.x, p.x.v[4 * k + 1] = xa.y, p.x.v[4 * k + 2] = xa.z, p.x.v[4 * k + 3] = xa.w;
-                p.y.v[4 * k] = ya.x, p.y.v[4 * k + 1] = ya.y, p.y.v[4 * k + 2] = ya.z, p.y.v[4 * k + 3] = ya.w;
-            }
-            // the other slot was read one full addition ago: safe to overwrite
-            if (e + 1 < end) issue(vn, slot ^ 1u);
-            const uint32_t vnn = e + 2 < end ? sorted[e + 2] : vn;
-            step(e, (v & 1) ? aff_neg(p) : p);
-            v = vn;
-            vn = vnn;
-        }
-    } else {
-        // one point ahead: the next random 96/192-byte fetch overlaps this mixed addition
-        Affine<L> p = fetch(v);
-        for (uint32_t e = beg; e < end; ++e) {
-            const uint32_t vn = e + 1 < end ? sorted[e + 1] : v;
-            const Affine<L> pn = fetch(vn);
-            step(e, (v & 1) ? aff_neg(p) : p);
-            v = vn;
-            p = pn;
-        }
-    }
-    store_jac<L>(partials, seg, acc);
-}
-
-// ------------------------------------------------------------------------------------
-// 4'. G1 accumulation in unsaturated radix 2^28 (mbls_fq28.hpp; round 5).  Same schedule as
-//     k_accumulate's LDS-DMA path -- chunks, bucket boundaries, the free first point and the
-//     mmadd second point, the next point staged in LDS -- with the lane arithmetic on 14 x 28-bit
-//     limbs: a column of a product is one v_mad_u64_u32 chain with no carry tracking (the 32-bit
-//     FIPS product pays a v_addc per mad, and on gfx950 every VALU instruction costs the same
-//     ~4 cycles: tools/valu_ceiling.hip).  Points are unpacked 8 bits low (x R 2^8 = x R',
-//     free), partials are written back in the library's canonical Montgomery words, so every
-//     other kernel is unchanged.  Same field values as jac_madd / jac_mmadd / jac_dbl, hence the
-//     same Jacobian partials, bit for bit (tools/fq28_bench.hip; the GPU parity suite).
-// ------------------------------------------------------------------------------------
-#ifndef MBLS_ACC_R28
-#define MBLS_ACC_R28 1
-#endif
-#ifndef MBLS_BS_R28
-#define MBLS_BS_R28 1  // light bucket sums (k_bucket_small, G1) in radix 2^28 too
-#endif
-#ifndef MBLS_ACC_XYZZ
-#define MBLS_ACC_XYZZ 1  // G1 accumulation and light / slice-chain bucket sums in XYZZ (r28::X28)
-#endif
-// a chunk partial's bytes: G1 partials are the accumulator's raw radix-2^28 XYZZ limbs when the
-// accumulation runs in XYZZ (4 x 14 words: no to_words conversion at the flush, which is divergent
-// -- a bucket boundary falls inside ~25% of the chunks, at a different step in every lane -- and no
-// unpack_shift8 when the bucket sums read them), Jacobian words otherwise
+// a chunk partial's bytes: the accumulator's raw radix-2^28 XYZZ limbs (4 x 14 words, per Fq2
+// component for G2): no to_words conversion at the flush, which is divergent -- a bucket boundary
+// falls inside ~25% of the chunks, at a different step in every lane -- and no unpack_shift8 when
+// the bucket sums read them
 template <class F>
-struct PartialBytes {
-    static constexpr size_t value = 3 * sizeof(F);  // Jacobian
-};
+struct PartialBytes;
 template <>
 struct PartialBytes<Fq> {
-    static constexpr size_t value = (MBLS_ACC_XYZZ && MBLS_ACC_R28 && MBLS_ACC_LDS && MBLS_BS_R28) ? 224 : 144;
+    static constexpr size_t value = 224;
 };
-#ifndef MBLS_ACC_G2_R28
-#define MBLS_ACC_G2_R28 1
-#endif
-#ifndef MBLS_ACC_G2_XYZZ
-#define MBLS_ACC_G2_XYZZ 1  // G2 accumulation and bucket sums in pair-sliced XYZZ (r28p::X28p), raw partials
-#endif
-#define MBLS_G2_XYZZ_PARTIALS (MBLS_ACC_G2_XYZZ && MBLS_ACC_G2_R28)
 template <>
 struct PartialBytes<Fq2> {
-    static constexpr size_t value = MBLS_G2_XYZZ_PARTIALS ? 448 : 288;
+    static constexpr size_t value = 448;
 };
-static_assert(!MBLS_ACC_XYZZ || (MBLS_ACC_R28 && MBLS_ACC_LDS && MBLS_BS_R28),
-              "XYZZ partials need the radix-2^28 accumulation and bucket sums");
-#ifndef MBLS_RED_R28
-#define MBLS_RED_R28 1  // G1's lane-mode reduction levels in radix 2^28 (k_reduce_scaled_r28)
-#endif
-#ifndef MBLS_BUCKETS_XYZZ
-#define MBLS_BUCKETS_XYZZ 1  // G1: the bucket sums stay raw XYZZ (224 B) for a lane-mode level 0
-#endif
-#ifndef MBLS_BUCKETS_XYZZ_G2
-#define MBLS_BUCKETS_XYZZ_G2 1  // G2: the same, pair-sliced (448 B)
-#endif
-// G1 with a lane-mode level 0 (every large MSM): k_bucket_small stores the bucket sums as raw XYZZ
-// limbs (store_xyzz28) and level 0 adds them in XYZZ (k_reduce_scaled_r28x): no x_to_jac per
-// bucket, add-2008-s instead of add-2007-bl in the level's chains, no unpack_shift8 on its loads
-template <class F>
-constexpr bool buckets_xyzz_ok() {
-    return (std::is_same<F, Fq>::value && MBLS_ACC_XYZZ && MBLS_RED_R28 && MBLS_BUCKETS_XYZZ) ||
-           (std::is_same<F, Fq2>::value && MBLS_G2_XYZZ_PARTIALS && MBLS_BUCKETS_XYZZ_G2);
-}
+// with a lane-mode level 0 (every large MSM) k_bucket_small stores the bucket sums as raw XYZZ
+// limbs too (store_xyzz28 / store_xyzz28p) and level 0 adds them in XYZZ (k_reduce_scaled_r28x /
+// _r28px): no x_to_jac per bucket, add-2008-s instead of add-2007-bl in the level's chains, no
+// unpack_shift8 on its loads
 template <class F>
 constexpr size_t xyzz_bucket_bytes() {
     return std::is_same<F, Fq>::value ? 224 : 448;
@@ -394,9 +261,6 @@ MBLS_DEV void store_jac28(uint8_t* __restrict__ partials, uint32_t seg, const r2
     store_jac<Fq>(partials, seg, out);
 }
 
-#ifndef MBLS_ACC_R28_PARK
-#define MBLS_ACC_R28_PARK 1
-#endif
 #ifndef MBLS_ACC_R28_MINW
 #define MBLS_ACC_R28_MINW 3  // waves per SIMD the register budget is sized for (variant builds: 2)
 #endif
@@ -418,21 +282,10 @@ __global__ __launch_bounds__(256, MBLS_ACC_R28_MINW) void k_accumulate_r28(const
     while (offsets[b + 1] <= beg) ++b;
     uint32_t seg = chunk_off[b] + (t - offsets[b] / chunk);
     uint32_t bend = offsets[b + 1];
-#if MBLS_ACC_XYZZ
     using Acc = r28::X28;
-#else
-    using Acc = r28::J28;
-#endif
     Acc acc = Acc::inf();
-    auto flush = [&](uint32_t sg) __attribute__((always_inline)) {
-#if MBLS_ACC_XYZZ
-        store_xyzz28(partials, sg, acc);
-#else
-        store_jac28(partials, sg, acc);
-#endif
-    };
+    auto flush = [&](uint32_t sg) __attribute__((always_inline)) { store_xyzz28(partials, sg, acc); };
     __shared__ uint4 stage[2][256 / 64][6][64];
-#if MBLS_ACC_R28_PARK
     // acc.y parked in the lane's half of the stage that the current point was just read from
     // (free until the next step's DMA), across the mixed addition's middle: 14 VGPRs fewer at
     // the register bound, where the compiler otherwise spilled ~30 VGPRs to scratch
@@ -466,7 +319,6 @@ __global__ __launch_bounds__(256, MBLS_ACC_R28_MINW) void k_accumulate_r28(const
             return r;
         }
     };
-#endif
     const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
     auto issue = [&](uint32_t vv, uint32_t slot) {
         uint32_t idx = vv >> 1;
@@ -508,18 +360,9 @@ __global__ __launch_bounds__(256, MBLS_ACC_R28_MINW) void k_accumulate_r28(const
             r28::F28 qy = r28::unpack_shift8(yw);
             if (v & 1) qy = r28::neg<r28::B512>(qy);  // -P: < 512 p, limbs < 2^30.4 (mbls_fq28.hpp)
             bool done = false;
-#if MBLS_ACC_R28_PARK
             ParkStage pk{&stage[slot][wv][0][ln]};
-#else
-            r28::ParkReg pk;
-#endif
-#if MBLS_ACC_XYZZ
-            if (MBLS_ACC_MMADD && e == beg + 1 && !acc.is_inf()) done = r28::xmmadd(acc, qx, qy);
+            if (e == beg + 1 && !acc.is_inf()) done = r28::xmmadd(acc, qx, qy);
             if (!done) r28::xmadd(acc, qx, qy, pk);
-#else
-            if (MBLS_ACC_MMADD && e == beg + 1 && !acc.is_inf()) done = r28::mmadd(acc, qx, qy);
-            if (!done) r28::madd(acc, qx, qy, pk);
-#endif
         }
         v = vn;
         vn = vnn;
@@ -528,25 +371,14 @@ __global__ __launch_bounds__(256, MBLS_ACC_R28_MINW) void k_accumulate_r28(const
 }
 
 // ------------------------------------------------------------------------------------
-// 4''. G2 accumulation in pair-sliced radix 2^28 (mbls_fq2_28.hpp; round 6).  k_accumulate's
-//     schedule over PAIRS of lanes (lane j: component j of every Fq2 value), with the next point
-//     prefetched into registers one addition ahead, the chunk's first point free and its second
-//     by mmadd; each lane's Fq2 product is one radix-2^28 product sum (no carry tracking).  The
-//     rare exceptional step (H = 0: equal or opposite points) converts the accumulator to words
-//     and takes jac_madd over PFq2.  Partials are stored in the library's canonical words: every
-//     other kernel is unchanged, and the partials equal k_accumulate<Fq2>'s bit for bit.
+// 4'. G2 accumulation in pair-sliced radix 2^28 XYZZ (mbls_fq2_28.hpp; round 6).  The G1
+//     kernel's schedule over PAIRS of lanes (lane j: component j of every Fq2 value), with the
+//     next point prefetched into registers one addition ahead, the chunk's first point free and
+//     its second by xmmadd; each lane's Fq2 product is one radix-2^28 product sum (no carry
+//     tracking).  Equal or opposite points (H = 0) are handled inside xmadd (xdbl / identity).
 // ------------------------------------------------------------------------------------
-#ifndef MBLS_ACC_G2_R28
-#define MBLS_ACC_G2_R28 1
-#endif
 #ifndef MBLS_ACC_G2_MINW
 #define MBLS_ACC_G2_MINW 2  // waves per SIMD the register budget is sized for
-#endif
-#ifndef MBLS_ACC_G2_LDS
-#define MBLS_ACC_G2_LDS 0  // 1: next point prefetched into LDS (LDS-DMA) instead of VGPRs
-#endif
-#ifndef MBLS_ACC_G2_XYZZ
-#define MBLS_ACC_G2_XYZZ 1  // G2 accumulation and bucket sums in pair-sliced XYZZ (r28p::X28p), raw partials
 #endif
 // G2 XYZZ partial k: lane j (component j) holds its 4 x 14 raw limbs at k * 448 + j * 224
 MBLS_DEV void store_xyzz28p(uint8_t* __restrict__ partials, uint32_t seg, const r28p::X28p& acc) {
@@ -561,27 +393,6 @@ MBLS_DEV void store_xyzz28p(uint8_t* __restrict__ partials, uint32_t seg, const 
     }
 #pragma unroll
     for (int j = 0; j < 14; ++j) q[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]);
-}
-MBLS_DEV void r28p_add_partial(r28p::X28p& acc, const uint8_t* __restrict__ partials, uint32_t k) {
-    const uint4* q = reinterpret_cast<const uint4*>(partials + (size_t)k * 448 + (pairdpp::odd() ? 224 : 0));
-    uint32_t w[56];
-#pragma unroll
-    for (int j = 0; j < 14; ++j) {
-        const uint4 u = q[j];
-        w[4 * j] = u.x, w[4 * j + 1] = u.y, w[4 * j + 2] = u.z, w[4 * j + 3] = u.w;
-    }
-    r28::F28 x, y, zz, zzz;
-    uint32_t zany = 0;
-#pragma unroll
-    for (int i = 0; i < 14; ++i) {
-        x.l[i] = w[i];
-        y.l[i] = w[14 + i];
-        zz.l[i] = w[28 + i];
-        zzz.l[i] = w[42 + i];
-        zany |= w[28 + i];
-    }
-    // the identity is zz = 0 on both lanes (pair-uniform predicate)
-    if (!r28p::both(zany == 0)) r28p::xadd(acc, x, y, zz, zzz);
 }
 MBLS_DEV void xadd_raw(r28p::X28p& acc, const uint32_t (&w)[56]) {
     r28::F28 x, y, zz, zzz;
@@ -602,14 +413,6 @@ MBLS_DEV Jacobian<PFq2> xyzz28p_to_words(const r28p::X28p& acc) {
     if (j.is_inf()) return Jacobian<PFq2>::inf();
     return {r28p::to_pf(j.x), r28p::to_pf(j.y), r28p::to_pf(j.z)};
 }
-MBLS_DEV void store_jac28p(uint8_t* __restrict__ partials, uint32_t seg, const r28p::J28p& acc) {
-    Jacobian<PFq2> out;
-    if (acc.is_inf())
-        out = Jacobian<PFq2>::inf();
-    else
-        out = {r28p::to_pf(acc.x), r28p::to_pf(acc.y), r28p::to_pf(acc.z)};
-    store_jac<PFq2>(partials, seg, out);
-}
 
 template <class F>  // F = Fq2 only (a template so only msm_g2.hip instantiates it)
 __global__ __launch_bounds__(256, MBLS_ACC_G2_MINW) void k_accumulate_r28p(const uint32_t* __restrict__ sorted,
@@ -629,52 +432,9 @@ __global__ __launch_bounds__(256, MBLS_ACC_G2_MINW) void k_accumulate_r28p(const
     while (offsets[b + 1] <= beg) ++b;
     uint32_t seg = chunk_off[b] + (t - offsets[b] / chunk);
     uint32_t bend = offsets[b + 1];
-#if MBLS_ACC_G2_XYZZ
     using Acc = r28p::X28p;
-#else
-    using Acc = r28p::J28p;
-#endif
     Acc acc = Acc::inf();
-    auto flush = [&](uint32_t sg) __attribute__((always_inline)) {
-#if MBLS_ACC_G2_XYZZ
-        store_xyzz28p(partials, sg, acc);
-#else
-        store_jac28p(partials, sg, acc);
-#endif
-    };
-#if MBLS_ACC_G2_LDS
-    // the next point's component (x: 3 x 16 B, y: 3 x 16 B per lane) prefetched into LDS by
-    // LDS-DMA, double-buffered per wave (the G1 kernel's stage): no 24 VGPRs held across the
-    // addition.  Stage: [slot][wave][piece][lane] x 16 B = 48 KiB per workgroup.
-    __shared__ uint4 stage[2][256 / 64][6][64];
-    const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
-    const uint32_t half = pairdpp::odd() ? 48u : 0u;
-    auto issue = [&](uint32_t vv, uint32_t slot) {
-        uint32_t idx = vv >> 1;
-        const uint8_t* src = idx >= nsplit ? phi : bases;
-        idx = idx >= nsplit ? idx - nsplit : idx;
-        const uint8_t* g = src + (size_t)idx * 192 + half;
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) const void*)(g + (k < 3 ? 16 * k : 96 + 16 * (k - 3))),
-                                             (__attribute__((address_space(3))) void*)&stage[slot][wv][k][0], 16, 0, 0);
-    };
-    uint32_t v = sorted[beg];
-    issue(v, 0);
-    uint32_t vn = beg + 1 < end ? sorted[beg + 1] : v;
-    for (uint32_t e = beg; e < end; ++e) {
-        const uint32_t slot = (e - beg) & 1;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this point's pieces have landed
-        Affine<PFq2> p;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const uint4 xa = stage[slot][wv][k][ln], ya = stage[slot][wv][3 + k][ln];
-            p.x.v.v[4 * k] = xa.x, p.x.v.v[4 * k + 1] = xa.y, p.x.v.v[4 * k + 2] = xa.z, p.x.v.v[4 * k + 3] = xa.w;
-            p.y.v.v[4 * k] = ya.x, p.y.v.v[4 * k + 1] = ya.y, p.y.v.v[4 * k + 2] = ya.z, p.y.v.v[4 * k + 3] = ya.w;
-        }
-        if (e + 1 < end) issue(vn, slot ^ 1u);  // the other slot was read one addition ago
-        const uint32_t vnn = e + 2 < end ? sorted[e + 2] : vn;
-#else
+    auto flush = [&](uint32_t sg) __attribute__((always_inline)) { store_xyzz28p(partials, sg, acc); };
     auto fetch = [&](uint32_t vv) {
         uint32_t idx = vv >> 1;
         const uint8_t* src = idx >= nsplit ? phi : bases;
@@ -686,7 +446,6 @@ __global__ __launch_bounds__(256, MBLS_ACC_G2_MINW) void k_accumulate_r28p(const
     for (uint32_t e = beg; e < end; ++e) {
         const uint32_t vn = e + 1 < end ? sorted[e + 1] : v;
         const Affine<PFq2> pn = fetch(vn);  // one point ahead: the gather overlaps this addition
-#endif
         if (e == bend) {  // bucket boundary inside the chunk: flush, move to the next bucket
             flush(seg);
             acc = Acc::inf();
@@ -700,37 +459,12 @@ __global__ __launch_bounds__(256, MBLS_ACC_G2_MINW) void k_accumulate_r28p(const
             const r28::F28 qx = r28::unpack_shift8(p.x.v.v);
             r28::F28 qy = r28::unpack_shift8(p.y.v.v);
             if (v & 1) qy = r28::carry(r28::neg<r28::B512>(qy));  // -P, normalised (mbls_fq2_28.hpp)
-#if MBLS_ACC_G2_XYZZ
             bool done = false;
-            if (MBLS_ACC_MMADD && e == beg + 1 && !acc.is_inf()) done = r28p::xmmadd(acc, qx, qy);
+            if (e == beg + 1 && !acc.is_inf()) done = r28p::xmmadd(acc, qx, qy);
             if (!done) r28p::xmadd(acc, qx, qy);  // equal / opposite points: xdbl / identity inside
-#else
-            if (acc.is_inf()) {
-                acc = {r28::fold(qx), r28::fold(qy), r28p::one()};
-            } else {
-                bool done = false;
-                if (MBLS_ACC_MMADD && e == beg + 1) done = r28p::mmadd(acc, qx, qy);
-                if (!done) done = r28p::madd(acc, qx, qy);
-                if (!done) {  // H = 0: doubling or the identity, in words (rare)
-                    const Jacobian<PFq2> aw = jac_madd(
-                        Jacobian<PFq2>{r28p::to_pf(acc.x), r28p::to_pf(acc.y), r28p::to_pf(acc.z)},
-                        (v & 1) ? aff_neg(p) : p);
-                    if (aw.is_inf())
-                        acc = r28p::J28p::inf();
-                    else
-                        acc = {r28::fold(r28p::from_pf(aw.x)), r28::fold(r28p::from_pf(aw.y)),
-                               r28::fold(r28p::from_pf(aw.z))};
-                }
-            }
-#endif
         }
-#if MBLS_ACC_G2_LDS
-        v = vn;
-        vn = vnn;
-#else
         v = vn;
         p = pn;
-#endif
     }
     flush(seg);
 }
@@ -903,8 +637,6 @@ MBLS_DEV bool load_j28(const uint8_t* __restrict__ base, size_t i, r28::F28& x, 
     z = r28::unpack_shift8(w[2]);
     return true;
 }
-// r28 XYZZ addition of chunk partial k (G1 with MBLS_ACC_XYZZ: the light path's and the slice
-// chains' form; raw limbs, store_xyzz28); the identity (zz = 0) adds nothing
 // the 56 raw words of XYZZ record k (224 B; `half` selects the odd lane's half of a 448-B pair record)
 MBLS_DEV void load_raw56(const uint8_t* __restrict__ recs, size_t off, uint32_t (&w)[56]) {
     const uint4* q = reinterpret_cast<const uint4*>(recs + off);
@@ -927,25 +659,17 @@ MBLS_DEV void xadd_raw(r28::X28& acc, const uint32_t (&w)[56]) {
     }
     if (zany) r28::xadd(acc, x, y, zz, zzz);
 }
+// XYZZ addition of chunk partial k (the light path's and the slice chains' form; raw limbs,
+// store_xyzz28 / store_xyzz28p); the identity (zz = 0) adds nothing
 MBLS_DEV void r28_add_partial(r28::X28& acc, const uint8_t* __restrict__ partials, uint32_t k) {
     uint32_t w[56];
     load_raw56(partials, (size_t)k * 224, w);
     xadd_raw(acc, w);
 }
-// r28 lane addition of Jacobian chunk partial k (G1 without MBLS_ACC_XYZZ)
-MBLS_DEV void r28_add_partial(r28::J28& acc, const uint8_t* __restrict__ partials, uint32_t k) {
-    const uint4* q = reinterpret_cast<const uint4*>(partials + (size_t)k * 144);
-    uint32_t w[3][12], zany = 0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const uint4 u = q[3 * c + j];
-            w[c][4 * j] = u.x, w[c][4 * j + 1] = u.y, w[c][4 * j + 2] = u.z, w[c][4 * j + 3] = u.w;
-        }
-#pragma unroll
-    for (int j = 0; j < 12; ++j) zany |= w[2][j];
-    if (zany) r28::jadd(acc, r28::unpack_shift8(w[0]), r28::unpack_shift8(w[1]), r28::unpack_shift8(w[2]));
+MBLS_DEV void r28p_add_partial(r28p::X28p& acc, const uint8_t* __restrict__ partials, uint32_t k) {
+    uint32_t w[56];
+    load_raw56(partials, (size_t)k * 448 + (pairdpp::odd() ? 224 : 0), w);
+    xadd_raw(acc, w);
 }
 
 // Slice plan (round 5): the slice length S adapts to the heavy partials T of the call, S =
@@ -962,9 +686,6 @@ MBLS_DEV void r28_add_partial(r28::J28& acc, const uint8_t* __restrict__ partial
 #ifndef MBLS_HEAVY_SLICE_MIN
 #define MBLS_HEAVY_SLICE_MIN 256
 #endif
-#ifndef MBLS_HEAVY_TRACE
-#define MBLS_HEAVY_TRACE 0
-#endif
 static constexpr uint32_t HEAVY_SLICE_MIN = MBLS_HEAVY_SLICE_MIN, HEAVY_LDS = 1024, HEAVY_GROUP = 16;
 
 // a bucket's row-layout sum (limb j on lane j of row 0 -- wave layout's leader row, or the row
@@ -972,7 +693,7 @@ static constexpr uint32_t HEAVY_SLICE_MIN = MBLS_HEAVY_SLICE_MIN, HEAVY_LDS = 10
 // (X, Y, Z^2, Z^3) the lane-mode level 0 reads (k_reduce_scaled_r28x).  Wave 0, all 64 lanes.
 template <class F>
 MBLS_DEV void store_bucket_row(uint8_t* __restrict__ buckets, uint32_t b, const RJac<F>& p, bool xb) {
-    if constexpr (std::is_same<F, Fq>::value && buckets_xyzz_ok<F>()) {
+    if constexpr (std::is_same<F, Fq>::value) {
         if (xb) {
             uint32_t w[3][12], zany = 0;
 #pragma unroll
@@ -995,7 +716,7 @@ MBLS_DEV void store_bucket_row(uint8_t* __restrict__ buckets, uint32_t b, const 
             return;
         }
     }
-    if constexpr (std::is_same<F, Fq2>::value && buckets_xyzz_ok<F>()) {
+    if constexpr (std::is_same<F, Fq2>::value) {
         if (xb) {  // every lane of wave 0 forms its pair component (c0 on even lanes, c1 on odd)
             const bool odd = pairdpp::odd();
             uint32_t w[3][12], zany = 0;
@@ -1035,10 +756,6 @@ MBLS_DEV void heavy_slices(const uint32_t* __restrict__ chunk_off, const uint8_t
     __shared__ uint32_t last, hfirst[HEAVY_LDS + 1], wred[4];
     const uint32_t nh = H.cnt[0];
     if (nh == 0) return;  // workgroup-uniform (random scalars: every slice workgroup leaves here)
-#if MBLS_HEAVY_TRACE  // diagnostic builds only: per-workgroup wall-clock stamps
-    const uint64_t tr0 = wall_clock64();
-    uint64_t trs = 0, trg = 0;
-#endif
     const bool planned = nh <= HEAVY_LDS;
     uint32_t S = HEAVY_SLICE, nsl = H.cnt[1];
     if (planned) {
@@ -1101,15 +818,10 @@ MBLS_DEV void heavy_slices(const uint32_t* __restrict__ chunk_off, const uint8_t
         // row addition's latency, but 16 rows summing 256 chains took 15 of them in series), then
         // the rows
         uint32_t live = min(CHAINS, c1 - c0);
-        if constexpr (std::is_same<L, Fq>::value && MBLS_BS_R28) {
-#if MBLS_ACC_XYZZ
+        if constexpr (std::is_same<L, Fq>::value) {
             r28::X28 xacc = r28::X28::inf();
             for (uint32_t k = c0 + j; k < c1; k += CHAINS) r28_add_partial(xacc, partials, k);
             r28::J28 acc = r28::x_to_jac(xacc);  // the lane tree below adds Jacobian chain sums
-#else
-            r28::J28 acc = r28::J28::inf();
-            for (uint32_t k = c0 + j; k < c1; k += CHAINS) r28_add_partial(acc, partials, k);
-#endif
             store_jac28(sh, j, acc);
             __syncthreads();
             for (; live > 16; live = (live + 1) / 2) {
@@ -1123,14 +835,9 @@ MBLS_DEV void heavy_slices(const uint32_t* __restrict__ chunk_off, const uint8_t
                 __syncthreads();
             }
         } else {
-            Jacobian<L> acc = Jacobian<L>::inf();
-            if constexpr (std::is_same<F, Fq2>::value && MBLS_G2_XYZZ_PARTIALS) {
-                r28p::X28p xacc = r28p::X28p::inf();
-                for (uint32_t k = c0 + j; k < c1; k += CHAINS) r28p_add_partial(xacc, partials, k);
-                acc = xyzz28p_to_words(xacc);  // the lane tree below adds Jacobian chain sums
-            } else {
-                for (uint32_t k = c0 + j; k < c1; k += CHAINS) acc = jac_add(acc, load_jac<L>(partials, k));
-            }
+            r28p::X28p xacc = r28p::X28p::inf();
+            for (uint32_t k = c0 + j; k < c1; k += CHAINS) r28p_add_partial(xacc, partials, k);
+            Jacobian<L> acc = xyzz28p_to_words(xacc);  // the lane tree below adds Jacobian chain sums
             store_jac<L>(sh, j, acc);
             __syncthreads();
             for (; live > 16; live = (live + 1) / 2) {
@@ -1143,9 +850,6 @@ MBLS_DEV void heavy_slices(const uint32_t* __restrict__ chunk_off, const uint8_t
         }
         using WIO = RedIO<F, MODE_WAVE>;
         const RJac<F> ssum = wave_sum16<F>(sh, live, [&](uint32_t k) { return WIO::ld(sh, k); });
-#if MBLS_HEAVY_TRACE
-        trs = wall_clock64();
-#endif
         if (threadIdx.x < 64) WIO::st(H.res, g, ssum);
         __threadfence();
         __syncthreads();
@@ -1162,9 +866,6 @@ MBLS_DEV void heavy_slices(const uint32_t* __restrict__ chunk_off, const uint8_t
             __threadfence();
             const RJac<F> gsum = wave_sum16<F>(sh, gs, [&](uint32_t k) { return WIO::ld(H.res, gl + k); });
             if (threadIdx.x < 64) WIO::st(H.res, gl, gsum);
-#if MBLS_HEAVY_TRACE
-            trg = wall_clock64();
-#endif
             __threadfence();
             __syncthreads();
             nsum = (ns + HEAVY_GROUP - 1) / HEAVY_GROUP, step = HEAVY_GROUP;
@@ -1172,13 +873,7 @@ MBLS_DEV void heavy_slices(const uint32_t* __restrict__ chunk_off, const uint8_t
         if (threadIdx.x == 0) last = atomicAdd(&H.done[e], 1u) + 1 == nsum ? 1u : 0u;
         __syncthreads();
         if (last) {  // this workgroup finished bucket b's last slice (group): sum the sums
-#if MBLS_HEAVY_TRACE
-            const uint64_t trf0 = wall_clock64();
-#endif
             __threadfence();
-#if MBLS_HEAVY_TRACE
-            const uint64_t trf1 = wall_clock64();
-#endif
             if (nsum <= 16) {  // workgroup-uniform
                 const RJac<F> tot = wave_sum16<F>(sh, nsum, [&](uint32_t k) { return WIO::ld(H.res, f0 + k * step); });
                 if (threadIdx.x < 64) store_bucket_row<F>(buckets, b, tot, xb);
@@ -1188,15 +883,7 @@ MBLS_DEV void heavy_slices(const uint32_t* __restrict__ chunk_off, const uint8_t
                 tot = row_tree<F>(tot, sh, r);
                 if (threadIdx.x < 64) store_bucket_row<F>(buckets, b, tot, xb);
             }
-#if MBLS_HEAVY_TRACE
-            const uint64_t trb = wall_clock64();
-            if (threadIdx.x == 0)
-                printf("HB g=%u e=%u t0=%llu ts=%llu tg=%llu tf0=%llu tf1=%llu tb=%llu\n", g, e, tr0, trs, trg, trf0, trf1, trb);
-#endif
         }
-#if MBLS_HEAVY_TRACE
-        else if (threadIdx.x == 0) printf("HS g=%u e=%u t0=%llu ts=%llu tg=%llu\n", g, e, tr0, trs, trg);
-#endif
         __syncthreads();  // sh and `last` are reused by the next slice
     }
 }
@@ -1234,24 +921,15 @@ __global__ __launch_bounds__(256, MBLS_BS_MINW) void k_bucket_small(const uint32
     if (t >= stop) return;
     const uint32_t b = perm[t];
     const uint32_t k0 = chunk_off[b], k1 = chunk_off[b + 1];
-    if constexpr (std::is_same<L, Fq>::value && MBLS_BS_R28) {
-        // radix 2^28: XYZZ sums of XYZZ partials (add-2008-s), one conversion per bucket (round 6);
-        // Jacobian jadd otherwise (round 5)
-#if MBLS_ACC_XYZZ
+    if constexpr (std::is_same<L, Fq>::value) {
+        // radix 2^28: XYZZ sums of XYZZ partials (add-2008-s), one conversion per bucket (round 6)
         r28::X28 acc = r28::X28::inf();
         for (uint32_t k = k0; k < k1; ++k) r28_add_partial(acc, partials, k);
         if (xb)
             store_xyzz28(buckets, b, acc);
         else
             store_jac28(buckets, b, r28::x_to_jac(acc));
-#else
-        r28::J28 acc = r28::J28::inf();
-        for (uint32_t k = k0; k < k1; ++k) r28_add_partial(acc, partials, k);
-        store_jac28(buckets, b, acc);
-#endif
-        return;
-    }
-    if constexpr (std::is_same<F, Fq2>::value && MBLS_G2_XYZZ_PARTIALS) {
+    } else {
         // pair-sliced radix-2^28 XYZZ sums of the raw XYZZ partials (round 6), one conversion
         r28p::X28p acc = r28p::X28p::inf();
         for (uint32_t k = k0; k < k1; ++k) r28p_add_partial(acc, partials, k);
@@ -1259,12 +937,7 @@ __global__ __launch_bounds__(256, MBLS_BS_MINW) void k_bucket_small(const uint32
             store_xyzz28p(buckets, b, acc);
         else
             store_jac<L>(buckets, b, xyzz28p_to_words(acc));
-        return;
     }
-    Jacobian<L> acc = Jacobian<L>::inf();
-    if (k1 > k0) acc = load_jac<L>(partials, k0);
-    for (uint32_t k = k0 + 1; k < k1; ++k) acc = jac_add(acc, load_jac<L>(partials, k));
-    store_jac<L>(buckets, b, acc);
 }
 
 // Scaled running-sum level: every level's outputs carry weight 1, so
@@ -1320,41 +993,9 @@ __global__ __launch_bounds__(256) void k_reduce_scaled(const uint8_t* __restrict
     IO::st(Uout, tid, S);
 }
 
-// G1's lane-mode level in radix 2^28 (round 5: the same outputs as k_reduce_scaled<Fq,
-// MODE_LANE> -- jadd / dbl compute the field values of jac_add / jac_dbl -- with ~20% fewer
-// instructions per addition on a chain that runs one wave per SIMD)
-template <class F>  // F = Fq only
-__global__ __launch_bounds__(256) void k_reduce_scaled_r28(const uint8_t* __restrict__ V, const uint8_t* __restrict__ U,
-                                                           uint32_t m_in, uint32_t seg_log, int Wg, int off,
-                                                           uint8_t* __restrict__ Vout, uint8_t* __restrict__ Uout) {
-    MBLS_TAIL_PRIO();
-    const uint32_t seg = 1u << seg_log;
-    const uint32_t m_out = (m_in + seg - 1) >> seg_log;
-    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= m_out * (uint32_t)Wg) return;
-    const uint32_t w = tid / m_out, q = tid % m_out;
-    const uint32_t k0 = q << seg_log;
-    const uint32_t k1 = min(k0 + seg, m_in);  // exclusive
-    const size_t base = (size_t)w * m_in;
-    r28::J28 R = r28::J28::inf(), S = r28::J28::inf();
-    r28::F28 x, y, z;
-    for (uint32_t t = k1; t-- > k0;) {
-        if (load_j28(V, base + t, x, y, z)) r28::jadd(R, x, y, z);  // R += V_t
-        if ((t - k0) + off != 0 && !R.is_inf()) r28::jadd(S, R.x, R.y, r28::carry(R.z));  // S += R
-        if (U && load_j28(U, base + t, x, y, z)) r28::jadd(S, x, y, z);  // S += U_t
-    }
-    if (Vout) {
-        for (uint32_t k = 0; k < seg_log; ++k) R = r28::dbl(R);
-        store_jac28(Vout, tid, R);
-    }
-    store_jac28(Uout, tid, S);
-}
-
-#ifndef MBLS_RED0_PREFETCH
-#define MBLS_RED0_PREFETCH 1  // level 0 loads bucket t - 1 before adding bucket t
-#endif
-// level 0 over raw XYZZ buckets (buckets_xyzz_ok, no U): the chain of k_reduce_scaled_r28 with
-// add-2008-s (r28::xadd, 12M + 2S) for its two additions per step, the outputs converted once
+// G1's lane-mode level 0 over raw XYZZ buckets (buckets_xyzz, no U) in radix 2^28: the chain of
+// k_reduce_scaled with add-2008-s (r28::xadd, 12M + 2S) for its two additions per step, the
+// outputs converted once.  Bucket t - 1 is loaded before bucket t is added.
 template <class F>  // F = Fq only
 __global__ __launch_bounds__(256) void k_reduce_scaled_r28x(const uint8_t* __restrict__ V, uint32_t m_in,
                                                             uint32_t seg_log, int Wg, int off,
@@ -1375,10 +1016,9 @@ __global__ __launch_bounds__(256) void k_reduce_scaled_r28x(const uint8_t* __res
         uint32_t cw[56];
 #pragma unroll
         for (int i = 0; i < 56; ++i) cw[i] = nw[i];
-        if (MBLS_RED0_PREFETCH && t > k0) load_raw56(V, (size_t)(base + t - 1) * 224, nw);
+        if (t > k0) load_raw56(V, (size_t)(base + t - 1) * 224, nw);
         xadd_raw(R, cw);                                                                   // R += V_t
         if ((t - k0) + off != 0 && !R.is_inf()) r28::xadd(S, R.x, R.y, R.zz, R.zzz);  // S += R
-        if (!MBLS_RED0_PREFETCH && t > k0) load_raw56(V, (size_t)(base + t - 1) * 224, nw);
     }
     if (Vout) {
         if (!R.is_inf())
@@ -1413,10 +1053,9 @@ __global__ __launch_bounds__(256) void k_reduce_scaled_r28px(const uint8_t* __re
         uint32_t cw[56];
 #pragma unroll
         for (int i = 0; i < 56; ++i) cw[i] = nw[i];
-        if (MBLS_RED0_PREFETCH && t > k0) load_raw56(V, (size_t)(base + t - 1) * 448 + half, nw);
+        if (t > k0) load_raw56(V, (size_t)(base + t - 1) * 448 + half, nw);
         xadd_raw(R, cw);                                                                    // R += V_t
         if ((t - k0) + off != 0 && !R.is_inf()) r28p::xadd(S, R.x, R.y, R.zz, R.zzz);  // S += R
-        if (!MBLS_RED0_PREFETCH && t > k0) load_raw56(V, (size_t)(base + t - 1) * 448 + half, nw);
         if (U) {  // S += U_t
             load_raw56(U, (size_t)(base + t) * 448 + half, cw);
             xadd_raw(S, cw);
@@ -1531,9 +1170,6 @@ __global__ __launch_bounds__(256) void k_reduce_tree4(const uint8_t* __restrict_
     }
 }
 
-#ifndef MBLS_FINAL_QUAD
-#define MBLS_FINAL_QUAD 1  // k_final_icicle's inversion on a lane quad (icicle_point_quad)
-#endif
 // final fold over window groups: sum_w 2^(c w) G_w  (one chain)
 template <class F, int MODE>
 MBLS_DEV auto final_fold(const uint8_t* __restrict__ windows, int Wg, int c) {
@@ -1545,12 +1181,12 @@ MBLS_DEV auto final_fold(const uint8_t* __restrict__ windows, int Wg, int c) {
     }
     return acc;
 }
-template <class F, int MODE>
+template <class F>
 __global__ void k_final(const uint8_t* __restrict__ windows, int Wg, int c, uint8_t* __restrict__ result) {
     MBLS_TAIL_PRIO();
-    using IO = RedIO<F, MODE>;
+    using IO = RedIO<F, MODE_WAVE>;
     if (IO::id() != 0) return;
-    IO::st(result, 0, final_fold<F, MODE>(windows, Wg, c));
+    IO::st(result, 0, final_fold<F, MODE_WAVE>(windows, Wg, c));
 }
 
 template <class F>
@@ -1661,31 +1297,19 @@ MBLS_DEV Fq row_to_lane(const RFq& a) {
 MBLS_DEV Fq2 row_to_lane(const RFq2& a) { return {row_to_lane(a.c0), row_to_lane(a.c1)}; }
 
 // k_final + k_jac_to_icicle in one launch (single ICICLE MSM, result on device): the wave's
-// folded point is gathered into lane 0, which normalises it and writes ICICLE's (x, y, 1)
-// straight into the caller's buffer (one launch gap and the result copy fewer)
+// folded point is gathered into every lane, the first lane quad normalises it (inv_quad) and
+// writes ICICLE's (x, y, 1) straight into the caller's buffer (one launch gap and the result
+// copy fewer)
 template <class F>
 __global__ __launch_bounds__(64) void k_final_icicle(const uint8_t* __restrict__ windows, int Wg, int c,
                                                      uint8_t* __restrict__ out) {
     MBLS_TAIL_PRIO();
-#if MBLS_HEAVY_TRACE
-    const uint64_t t0 = wall_clock64();
-#endif
     const RJac<F> acc = final_fold<F, MODE_WAVE>(windows, Wg, c);
     Jacobian<F> p;
     p.x = row_to_lane(acc.x);
     p.y = row_to_lane(acc.y);
     p.z = row_to_lane(acc.z);
-#if MBLS_HEAVY_TRACE
-    const uint64_t t1 = wall_clock64();
-#endif
-#if MBLS_FINAL_QUAD
     if (threadIdx.x < 4) icicle_point_quad<F>(p, out, 0);
-#else
-    if (threadIdx.x == 0) icicle_point<F>(p, out, 0);
-#endif
-#if MBLS_HEAVY_TRACE
-    if (threadIdx.x == 0) printf("FIN fold=%llu inv=%llu\n", t1 - t0, wall_clock64() - t1);
-#endif
 }
 
 template <class F>
@@ -1794,25 +1418,27 @@ struct MsmScratchSizes {
 #endif
 inline uint32_t wave_min_chains(bool fq2 = false) { return fq2 ? MBLS_WAVE_MIN_G2 : MBLS_WAVE_MIN; }
 
-// raw XYZZ buckets for this plan (buckets_xyzz_ok, level 0 in lanes)
+// raw XYZZ buckets for this plan (level 0 in lanes)
 template <class F>
 inline bool buckets_xyzz(const MsmPlan& P) {
-    return buckets_xyzz_ok<F>() && P.levels > 0 && P.mode[0] == MODE_LANE;
+    return P.levels > 0 && P.mode[0] == MODE_LANE;
 }
-#ifndef MBLS_RED_RAW_G2
-#define MBLS_RED_RAW_G2 1  // G2 lane levels after level 0 take raw pair XYZZ records from the level before
-#endif
-// a level output record's bytes: raw pair XYZZ (448) when G2 chains lane levels, else Jacobian
+// a level output record's bytes: raw pair XYZZ (448) when G2 chains lane levels (they take raw
+// records from the level before), else Jacobian
 template <class F>
-inline size_t level_bytes(const MsmPlan& P, size_t jac) {
-    return (std::is_same<F, Fq2>::value && MBLS_RED_RAW_G2 && buckets_xyzz<F>(P) && P.levels > 1 &&
-            P.mode[1] == MODE_LANE)
+inline size_t level_bytes(const MsmPlan& P) {
+    return (std::is_same<F, Fq2>::value && buckets_xyzz<F>(P) && P.levels > 1 && P.mode[1] == MODE_LANE)
                ? xyzz_bucket_bytes<F>()
-               : jac;
+               : GroupTraits<F>::JAC;
 }
-// bkt: a bucket sum's bytes (jac, or 224 for raw XYZZ buckets)
-inline MsmScratchSizes msm_scratch_sizes(const MsmPlan& P, size_t jac, size_t aff, uint32_t max_chunks, size_t part,
-                                         size_t bkt, size_t lvl) {
+template <class F>
+inline MsmScratchSizes msm_scratch_sizes(const MsmPlan& P) {
+    constexpr size_t jac = GroupTraits<F>::JAC, aff = GroupTraits<F>::AFF;
+    // the chunk count is data dependent (a short last chunk per bucket): its bound
+    const uint32_t max_chunks = (uint32_t)(P.contributions / P.chunk + P.TB + 1);
+    const size_t part = PartialBytes<F>::value;                                // a chunk partial's bytes
+    const size_t bkt = buckets_xyzz<F>(P) ? xyzz_bucket_bytes<F>() : jac;  // a bucket sum's bytes
+    const size_t lvl = level_bytes<F>(P);                                      // a level record's bytes
     MsmScratchSizes z;
     // the per-call image table; with bstride > 1 also the compact copy of the points (2n rows)
     z.phi = P.split > 1 && !P.prepared ? align_up(P.pts / P.split * (P.split - 1 + (P.bstride > 1 ? 1 : 0)) * aff) : 0;
@@ -1851,11 +1477,11 @@ inline MsmScratchSizes msm_scratch_sizes(const MsmPlan& P, size_t jac, size_t af
                      4);
     z.owner = align_up((size_t)max_chunks * 4);
     z.first = align_up((NC / P.chunk + 2) * 4);
-    z.partials = align_up((size_t)max_chunks * part);  // part: a chunk partial's bytes (PartialBytes)
+    z.partials = align_up((size_t)max_chunks * part);
     z.buckets = align_up((size_t)P.TB * bkt);
     // V / U ping-pong halves sized for the widest level's outputs (k_reduce_scaled)
     const size_t mo0 = P.levels ? (P.level_m[0] + P.seg(0) - 1) / P.seg(0) : 1;
-    z.levelT = align_up(2 * mo0 * P.Wg * lvl);  // lvl: a level record's bytes (level_bytes)
+    z.levelT = align_up(2 * mo0 * P.Wg * lvl);
     z.levelR = align_up(2 * mo0 * P.Wg * lvl);
     z.windows = align_up((size_t)P.Wg * jac);
     return z;
@@ -1869,18 +1495,13 @@ inline bool debug_enabled() {
     return v;
 }
 
-// the accumulation kernel instance: G1 at <= 168 VGPRs (3 waves per SIMD; -DMBLS_ACC_W3=0: 1)
-#ifndef MBLS_ACC_W3
-#define MBLS_ACC_W3 1
-#endif
+// the accumulation kernel instance
 using AccKernel = void (*)(const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, uint32_t,
                            const uint8_t*, const uint8_t*, uint32_t, uint32_t, uint8_t*);
 template <class F>
 inline AccKernel accumulate_kernel() {
-    if constexpr (std::is_same<F, Fq>::value && MBLS_ACC_R28 && MBLS_ACC_LDS) return k_accumulate_r28<F>;
-    else if constexpr (std::is_same<F, Fq2>::value && MBLS_ACC_G2_R28) return k_accumulate_r28p<F>;
-    else if constexpr (std::is_same<F, Fq>::value && MBLS_ACC_W3) return k_accumulate<F, 3>;
-    else return k_accumulate<F, 1>;
+    if constexpr (std::is_same<F, Fq>::value) return k_accumulate_r28<F>;
+    else return k_accumulate_r28p<F>;
 }
 
 // contributions per accumulation thread: CHUNK (16), or an eighth of the average bucket when
@@ -1927,10 +1548,7 @@ inline void launch_reduce_scaled(int mode, const uint8_t* V, const uint8_t* U, u
         hipLaunchKernelGGL(k_reduce_tree4<F>, dim3(chains), dim3(256), 0, s, V, U, m_in, Vo, Uo);
         return;
     }
-    if (mode == MODE_LANE && std::is_same<F, Fq>::value && MBLS_RED_R28)
-        hipLaunchKernelGGL((k_reduce_scaled_r28<F>), dim3((chains + 255) / 256), dim3(256), 0, s, V, U, m_in, seg_log, Wl,
-                           off, Vo, Uo);
-    else if (mode == MODE_LANE)
+    if (mode == MODE_LANE)  // the one fallback: a shipped plan's lane levels all read raw XYZZ records (msm_device)
         hipLaunchKernelGGL((k_reduce_scaled<F, MODE_LANE>), dim3((chains * LN + 255) / 256), dim3(256), 0, s, V, U, m_in,
                            seg_log, Wl, off, Vo, Uo);
     else if (mode == MODE_ROW)
@@ -1972,7 +1590,7 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
                         uint8_t* icicle_out = nullptr, const TailPipe* pipe = nullptr,
                         hipEvent_t acc_event = nullptr) {
     Arena& arena = ctx.arena;
-    constexpr size_t JAC = GroupTraits<F>::JAC, AFF = GroupTraits<F>::AFF;
+    constexpr size_t AFF = GroupTraits<F>::AFF;
     constexpr uint32_t LN = LaneOf<F>::LANES;  // lanes per chain in the lane-mode kernels
     // mbls_msm_accumulate_event: recorded after the accumulation launch below, or wherever this
     // function returns before it (an empty MSM, an error)
@@ -1985,11 +1603,8 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
     }
     const uint32_t TB = P.TB;
     const size_t NC = P.contributions;
-    const uint32_t max_chunks = (uint32_t)(NC / P.chunk + TB + 1);
     const bool xb = buckets_xyzz<F>(P);
-    MsmScratchSizes z =
-        msm_scratch_sizes(P, JAC, AFF, max_chunks, PartialBytes<F>::value, xb ? xyzz_bucket_bytes<F>() : JAC,
-                          level_bytes<F>(P, JAC));
+    const MsmScratchSizes z = msm_scratch_sizes<F>(P);
     uint32_t* keys = (uint32_t*)arena.take(z.keys);
     uint32_t* vals = (uint32_t*)arena.take(z.vals);
     uint32_t* ranks = (uint32_t*)arena.take(z.ranks);
@@ -2142,7 +1757,7 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
         ProfScope ps_red("msm.reduce", st);  // the levels only (k_final has its own scope)
         // scaled running-sum levels (k_reduce_scaled): V / U ping-pong in levelR / levelT, the
         // last level writes the window sums straight into `windows`
-        const size_t half = ((P.level_m[0] + P.seg(0) - 1) / P.seg(0)) * (size_t)P.Wg * level_bytes<F>(P, JAC);
+        const size_t half = ((P.level_m[0] + P.seg(0) - 1) / P.seg(0)) * (size_t)P.Wg * level_bytes<F>(P);
         uint8_t* vb[2] = {levelR, levelR + half};
         uint8_t* ub[2] = {levelT, levelT + half};
         const uint8_t* V = buckets;
@@ -2154,26 +1769,19 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
             const bool last = l == P.levels - 1;
             uint8_t* Vo = last ? nullptr : vb[l & 1];
             uint8_t* Uo = last ? windows : ub[l & 1];
-            bool done = false;
-            if constexpr (buckets_xyzz_ok<F>()) {
-                if (raw_in) {  // a lane level (level 0, or G2's lane levels after it)
-                    const uint32_t chains = m_out * (uint32_t)P.Wg;
-                    if constexpr (std::is_same<F, Fq>::value) {
-                        hipLaunchKernelGGL((k_reduce_scaled_r28x<F>), dim3((chains + 255) / 256), dim3(256), 0, st, V,
-                                           m_in, P.seg_log[0], P.Wg, 1, Vo, Uo);
-                        raw_in = false;
-                    } else {
-                        const bool raw_out = MBLS_RED_RAW_G2 && !last && P.mode[l + 1] == MODE_LANE;
-                        hipLaunchKernelGGL((k_reduce_scaled_r28px<F>), dim3((2 * chains + 255) / 256), dim3(256), 0, st,
-                                           V, U, m_in, P.seg_log[l], P.Wg, l == 0 ? 1 : 0, Vo, Uo, raw_out ? 1 : 0);
-                        raw_in = raw_out;
-                    }
-                    done = true;
-                }
+            const uint32_t chains = m_out * (uint32_t)P.Wg;
+            if (!raw_in) {
+                launch_reduce_scaled<F>(P.mode[l], V, U, m_in, P.seg_log[l], P.Wg, l == 0 ? 1 : 0, Vo, Uo, chains, st);
+            } else if constexpr (std::is_same<F, Fq>::value) {  // lane level 0
+                hipLaunchKernelGGL((k_reduce_scaled_r28x<F>), dim3((chains + 255) / 256), dim3(256), 0, st, V, m_in,
+                                   P.seg_log[0], P.Wg, 1, Vo, Uo);
+                raw_in = false;
+            } else {  // G2: lane level 0, or the lane levels after it
+                const bool raw_out = !last && P.mode[l + 1] == MODE_LANE;
+                hipLaunchKernelGGL((k_reduce_scaled_r28px<F>), dim3((2 * chains + 255) / 256), dim3(256), 0, st, V, U,
+                                   m_in, P.seg_log[l], P.Wg, l == 0 ? 1 : 0, Vo, Uo, raw_out ? 1 : 0);
+                raw_in = raw_out;
             }
-            if (!done)
-                launch_reduce_scaled<F>(P.mode[l], V, U, m_in, P.seg_log[l], P.Wg, l == 0 ? 1 : 0, Vo, Uo,
-                                        m_out * (uint32_t)P.Wg, st);
             V = Vo;
             U = Uo;
         }
@@ -2183,7 +1791,7 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
         if (icicle_out)
             hipLaunchKernelGGL(k_final_icicle<F>, dim3(1), dim3(64), 0, st, windows, P.Wg, P.c, icicle_out);
         else
-            hipLaunchKernelGGL((k_final<F, MODE_WAVE>), dim3(1), dim3(64), 0, st, windows, P.Wg, P.c, result);
+            hipLaunchKernelGGL(k_final<F>, dim3(1), dim3(64), 0, st, windows, P.Wg, P.c, result);
     }
     MBLS_TRY(hipGetLastError());
     return MBLS_SUCCESS;
@@ -2199,9 +1807,6 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
 // sharded multi-GPU MSM: partials are summed before the one normalisation)
 enum MsmEntry : int { MSM_RAW = 0, MSM_ICICLE = 1, MSM_JACOBIAN = 2 };
 
-#ifndef MBLS_PINNED_ZERO_COPY
-#define MBLS_PINNED_ZERO_COPY 1  // variant builds: 0 = always stage host scalars
-#endif
 template <class F>
 eIcicleError msm_call(const void* scalars, const void* bases, int msm_size, const MSMConfig* cfg, void* results,
                       int entry) {
@@ -2258,11 +1863,7 @@ eIcicleError msm_call(const void* scalars, const void* bases, int msm_size, cons
     if (debug_enabled())
         fprintf(stderr, "[mbls] msm n=%d c=%d W=%d Wg=%d split=%d TB=%u contributions=%zu chunk=%u levels=%d\n", msm_size,
                 P.c, P.W, P.Wg, P.split, P.TB, P.contributions, P.chunk, P.levels);
-    uint32_t max_chunks = (uint32_t)(P.contributions / P.chunk + P.TB + 1);
-    size_t scratch =
-        msm_scratch_sizes(P, JAC, AFF, max_chunks, PartialBytes<F>::value,
-                          buckets_xyzz<F>(P) ? xyzz_bucket_bytes<F>() : JAC, level_bytes<F>(P, JAC))
-            .total();
+    const size_t scratch = msm_scratch_sizes<F>(P).total();
     const bool piped = batch > 1 && batch_pipe() > 0;
     er = lease.reserve(st_s + st_b + st_r + scratch * (piped ? 2 : 1) + 4096);
     if (er != MBLS_SUCCESS) return er;
@@ -2279,7 +1880,7 @@ eIcicleError msm_call(const void* scalars, const void* bases, int msm_size, cons
         // copy is written and re-read.  Otherwise: a PCIe copy kernel (pinned)
         // or hipMemcpyAsync (pageable, or another device's memory for multi-device shards).
         const bool read_once = P.split > 1 || scal_mont;
-        const void* alias = read_once && MBLS_PINNED_ZERO_COPY ? pinned_host_device_pointer(scalars) : nullptr;
+        const void* alias = read_once ? pinned_host_device_pointer(scalars) : nullptr;
         if (alias) {
             d_s = static_cast<const uint8_t*>(alias);
         } else {

@@ -49,18 +49,6 @@ namespace mbls {
 #ifndef MBLS_NTT_THREADS
 #define MBLS_NTT_THREADS 256
 #endif
-#ifndef MBLS_NTT_DIRECT
-#define MBLS_NTT_DIRECT 1  // the pass's last stage group stores straight from registers (k_ntt_pass)
-#endif
-#ifndef MBLS_NTT_XCD
-#define MBLS_NTT_XCD 0  // 1: tiles of adjacent columns on the same XCD (shared L2 lines)
-#endif
-// diagnostic variant builds only (results WRONG, never shipped): 1 = no twiddle loads (a
-// register value instead), 2 = no barrier between stage pairs, 3 = no tile load from HBM (the
-// LDS tile is used as found), 4 = no tile store to HBM -- to price those costs
-#ifndef MBLS_NTT_EXP
-#define MBLS_NTT_EXP 0
-#endif
 static constexpr int NTT_TILE_LOG = MBLS_NTT_TILE_LOG;
 static constexpr int NTT_TILE = 1 << NTT_TILE_LOG;  // elements per workgroup tile
 static constexpr int NTT_THREADS = MBLS_NTT_THREADS;
@@ -261,18 +249,14 @@ __global__ __launch_bounds__(NTT_THREADS, 5) void k_ntt_pass(uint8_t* __restrict
 #pragma clang loop vectorize(disable) interleave(disable)
         for (uint32_t e = threadIdx.x; e < T; e += NTT_THREADS) {
             const uint32_t c = e & (C - 1), t = e >> logC;
-            if (MBLS_NTT_EXP == 3) {
-                if (e == 0xffffffffu) st2(lds, e, ld2(in, e));  // never: keeps the loop's shape
-            } else {
-                st2(lds, FIRST ? bitrev(t, L) * C + c : e, ld2(in + 2 * g.poly, src_of(g, e)));
-            }
+            st2(lds, FIRST ? bitrev(t, L) * C + c : e, ld2(in + 2 * g.poly, src_of(g, e)));
         }
         __syncthreads();
         // ---- L DIT stages: pairs of stages as radix-4 (2 x 2) butterflies in registers (one LDS
         // round trip and one barrier per pair), an odd last stage as radix-2
         const uint32_t lo_base = FIRST ? 0u : g.lo0;
         uint4* o = out + 2 * g.poly;
-        // the last stage group (MBLS_NTT_DIRECT) stores its outputs straight to HBM from registers:
+        // the last stage group stores its outputs straight to HBM from registers:
         // no LDS round trip, barrier or separate store loop; (row, c) of the tile -> its position
         auto put = [&](uint32_t row, uint32_t c, Fr v) {
             if (SCALE) v = v * scale;  // v < 2r, scale < r: the reduced product is canonical
@@ -281,7 +265,7 @@ __global__ __launch_bounds__(NTT_THREADS, 5) void k_ntt_pass(uint8_t* __restrict
         };
         int l = 1;
         for (; l + 1 <= L; l += 2) {
-            const bool fin = MBLS_NTT_DIRECT && l + 2 > L;  // the last pair, no radix-2 stage after it
+            const bool fin = l + 2 > L;  // the last pair, no radix-2 stage after it
             const uint32_t h = 1u << (l - 1);  // stage l pairs rows (t, t + h), stage l + 1 rows (t, t + 2h)
             const int s = s0 + l;              // global stage of the first of the pair
             const uint32_t t1 = (1u << (s - 1)) - 1, t2 = (1u << s) - 1;  // stage tables s, s + 1
@@ -304,7 +288,6 @@ __global__ __launch_bounds__(NTT_THREADS, 5) void k_ntt_pass(uint8_t* __restrict
                 w3 = ldtw(twa, twb, twc, t2 + jl + (h << s0));
                 Fr x0 = ld2(lds, e0), x1 = ld2(lds, e0 + stride), x2 = ld2(lds, e0 + 2 * stride),
                    x3 = ld2(lds, e0 + 3 * stride);
-                if (MBLS_NTT_EXP == 1) w1 = w2 = w3 = r29::unpack(x0);
                 // stage l: (x0, x1), (x2, x3) share twiddle w_(2^s)^j
                 if (!triv) {
                     x1 = r29::mul_words(x1, w1);
@@ -327,7 +310,7 @@ __global__ __launch_bounds__(NTT_THREADS, 5) void k_ntt_pass(uint8_t* __restrict
                 }
             }
             if (fin) return;
-            if (MBLS_NTT_EXP != 2) __syncthreads();
+            __syncthreads();
         }
         if (l == L) {  // odd stage count: one radix-2 stage
             const uint32_t half = 1u << (l - 1);
@@ -344,19 +327,13 @@ __global__ __launch_bounds__(NTT_THREADS, 5) void k_ntt_pass(uint8_t* __restrict
                 const Fr a = ld2(lds, t0 * C + c);
                 Fr b = ld2(lds, t1 * C + c);
                 if (l > 1 || !FIRST) b = r29::mul_words(b, w);
-                if (MBLS_NTT_DIRECT) {
-                    put(t0, c, add_2r(a, b));
-                    put(t1, c, sub_2r(a, b));
-                } else {
-                    st2(lds, t0 * C + c, add_2r(a, b));
-                    st2(lds, t1 * C + c, sub_2r(a, b));
-                }
+                put(t0, c, add_2r(a, b));
+                put(t1, c, sub_2r(a, b));
             }
-            if (MBLS_NTT_DIRECT) return;
-            __syncthreads();
+            return;
         }
 
-        // ---- store (L = 0 only, or MBLS_NTT_DIRECT = 0)
+        // ---- store (a pass with L = 0 only: every stage group above returns)
         for (uint32_t e = threadIdx.x; e < T; e += NTT_THREADS) {
             Fr v;
             uint32_t dst;
@@ -371,7 +348,6 @@ __global__ __launch_bounds__(NTT_THREADS, 5) void k_ntt_pass(uint8_t* __restrict
             }
             if (SCALE) v = v * scale;  // v < 2r, scale < r: the reduced product is canonical
             else if (LAST) reduce_once(v);
-            if (MBLS_NTT_EXP == 4 && (v.v[0] ^ v.v[7]) != 0x12345u) continue;  // (almost) never stores
             st2(o, dst, v);
         }
     }

@@ -1,6 +1,6 @@
 #!/bin/bash
 # library variant with one source compiled differently (every other object from build/):
-#   tools/build_variant.sh NAME SOURCE "-DFLAG=..."   e.g.  tools/build_variant.sh v_g2lds msm_g2 "-DMBLS_ACC_G2_LDS=1"
+#   tools/build_variant.sh NAME SOURCE "-DFLAG=..."   e.g.  tools/build_variant.sh v_g2w1 msm_g2 "-DMBLS_ACC_G2_MINW=1"
 #   -> midnight-bls12-381-cuda_amd/lib/NAME.so
 set -e
 cd "$(dirname "$0")/../midnight-bls12-381-cuda_amd"

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """G2 MSM 2^20 wall time (config #5's inputs, ICICLE entry, device operands): median of --reps
-timed calls after one warm-up, and the result digest (to compare settings).  A/B helper:
-  for E in "" "MBLS_PSI_SERIAL=1"; do env $E python3 tools/g2_time.py; done"""
+timed calls after one warm-up, and the result digest (to compare library variants: MBLS_LIB)."""
 import argparse
 import hashlib
 import os
