@@ -227,6 +227,39 @@ eIcicleError bls12_381_g2_projective_to_affine(const mbls_g2_projective_t* input
                                                mbls_g2_affine_t* output);
 
 /* ------------------------------------------------------------------------------------ */
+/* batch scalar multiplication: output[i] = scalars[i] * bases[i], independent variable-base
+ * multiplications.  The reference declares bls12_381_g1_scalar_mul (point_ops.cu:1149) and
+ * bls12_381_g1_scalar_mul_glv (:1019) behind GLV_ENABLED, which its build leaves off; here both
+ * names run one implementation (always the GLV split).  The G2 entry has no reference counterpart.
+ *   scalars: 32 bytes, STANDARD form; any 256-bit value k is accepted and the result is k * P
+ *     for the integer k, which on the order-r subgroup is (k mod r) * P (the reduction the raw MSM
+ *     entry applies).  The mbls_* forms read Montgomery scalars when scalars_montgomery is set.
+ *   bases: Montgomery affine; the identity is the all-zero point and gives the identity for every
+ *     scalar.  Bases are ASSUMED to lie in the order-r subgroup, as for the MSM: the GLV / psi
+ *     splits rely on phi = [lambda] and psi = [z], which hold only there (not checked).
+ *   output: Jacobian Montgomery (X, Y, Z), x = X/Z^2, y = Y/Z^3, identity Z = 0 -- the form
+ *     bls12_381_g*_projective_to_affine takes.  Input and output must not overlap.
+ *   placement: config->is_a_on_device the bases, is_b_on_device the scalars, is_result_on_device
+ *     the output (point_ops.cu:1044-1046).  Host buffers are staged through the leased scratch
+ *     context; a host output is synchronous, a device output synchronises unless is_async.
+ *     batch_size and columns_batch are not read.
+ *   errors: a null pointer, a null config, size <= 0 or size > 2^26 give INVALID_ARGUMENT before
+ *     any device work (point_ops.cu:1027-1035).
+ *   timing: NOT constant time -- table lookups and branches depend on the scalar's digits, like
+ *     the MSM's bucket sort.  Do not use with secret scalars where timing is observable.       */
+/* ------------------------------------------------------------------------------------ */
+eIcicleError bls12_381_g1_scalar_mul(const mbls_g1_affine_t* bases, const mbls_fr_t* scalars, int size,
+                                     const VecOpsConfig* config, mbls_g1_projective_t* output);
+eIcicleError bls12_381_g1_scalar_mul_glv(const mbls_g1_affine_t* bases, const mbls_fr_t* scalars, int size,
+                                         const VecOpsConfig* config, mbls_g1_projective_t* output);
+eIcicleError bls12_381_g2_scalar_mul(const mbls_g2_affine_t* bases, const mbls_fr_t* scalars, int size,
+                                     const VecOpsConfig* config, mbls_g2_projective_t* output);
+eIcicleError mbls_g1_scalar_mul(const mbls_g1_affine_t* bases, const mbls_fr_t* scalars, int size,
+                                bool scalars_montgomery, const VecOpsConfig* config, mbls_g1_projective_t* output);
+eIcicleError mbls_g2_scalar_mul(const mbls_g2_affine_t* bases, const mbls_fr_t* scalars, int size,
+                                bool scalars_montgomery, const VecOpsConfig* config, mbls_g2_projective_t* output);
+
+/* ------------------------------------------------------------------------------------ */
 /* library utilities (no reference counterpart; used by the host API, tests and bench)   */
 /* ------------------------------------------------------------------------------------ */
 const char* mbls_version(void);

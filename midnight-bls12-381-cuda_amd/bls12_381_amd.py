@@ -78,6 +78,8 @@ EXPORTED = [
     "mbls_g1_msm_multi_device", "mbls_g2_msm_multi_device", "bls12_381_vector_sum",
     "bls12_381_g1_affine_to_projective", "bls12_381_g1_projective_to_affine", "bls12_381_g2_projective_to_affine",
     "mbls_msm_plan", "mbls_msm_accumulate_event", "mbls_msm_accumulate_event_drop", "mbls_msm_precompute_strict",
+    "bls12_381_g1_scalar_mul", "bls12_381_g1_scalar_mul_glv", "bls12_381_g2_scalar_mul",
+    "mbls_g1_scalar_mul", "mbls_g2_scalar_mul",
 ]
 
 _LIB = None
@@ -123,6 +125,9 @@ def lib():
         "mbls_msm_plan": [i32, i32, P, P],
         "mbls_msm_accumulate_event": [P, P], "mbls_msm_accumulate_event_drop": [P],
         "mbls_msm_precompute_strict": [i32],
+        "bls12_381_g1_scalar_mul": [P, P, i32, P, P], "bls12_381_g1_scalar_mul_glv": [P, P, i32, P, P],
+        "bls12_381_g2_scalar_mul": [P, P, i32, P, P],
+        "mbls_g1_scalar_mul": [P, P, i32, b, P, P], "mbls_g2_scalar_mul": [P, P, i32, b, P, P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -268,6 +273,23 @@ def convert_points(group, direction, pts, out=None, stream=None, is_async=False)
         out = np.zeros((n, words), dtype=np.uint64)
     cfg = vec_config(is_a_on_device=_is_dev(pts), is_result_on_device=_is_dev(out), stream=stream, is_async=is_async)
     check(getattr(lib(), name)(_p(pts), n, ctypes.byref(cfg), _p(out)), name)
+    return out
+
+
+def scalar_mul(group, bases, scalars, *, scalars_mont=False, out=None, stream=None, is_async=False):
+    """Batch scalar multiplication out[i] = scalars[i] * bases[i] (mbls_g*_scalar_mul): `bases`
+    (n, 12 | 24) uint64 Montgomery affine, `scalars` (n, 4) uint64, standard form unless
+    scalars_mont; each numpy (host) or torch (device).  Returns (n, 18 | 36) Jacobian Montgomery
+    (identity Z = 0), host numpy unless `out` is a device tensor; convert_points(group,
+    "to_affine", ...) gives affine points.  Bases are assumed to lie in the order-r subgroup."""
+    n = bases.shape[0]
+    assert scalars.shape[0] == n
+    if out is None:
+        out = np.zeros((n, 18 if group == "g1" else 36), dtype=np.uint64)
+    cfg = vec_config(is_a_on_device=_is_dev(bases), is_b_on_device=_is_dev(scalars), is_result_on_device=_is_dev(out),
+                     stream=stream, is_async=is_async)
+    name = "mbls_g1_scalar_mul" if group == "g1" else "mbls_g2_scalar_mul"
+    check(getattr(lib(), name)(_p(bases), _p(scalars), n, bool(scalars_mont), ctypes.byref(cfg), _p(out)), name)
     return out
 
 
