@@ -90,6 +90,35 @@ void* Arena::take(size_t bytes) {
     return p;
 }
 
+eIcicleError Staging::open() {
+    if (n_ > MAX_BLOCKS) return MBLS_INVALID_ARGUMENT;
+    size_t sum = 0;
+    for (int i = 0; i < n_; ++i) sum += align_up(blocks_[i].bytes);
+    if (!always_ && !sum) return MBLS_SUCCESS;
+    lease_.emplace(st_);
+    if (!*lease_) return lease_->error();
+    const eIcicleError er = lease_->reserve(sum);
+    if (er != MBLS_SUCCESS) return er;
+    for (int i = 0; i < n_; ++i) {
+        const Block& b = blocks_[i];
+        *b.p = static_cast<uint8_t*>((*lease_)->arena.take(b.bytes));
+        if (b.kind == IN) MBLS_TRY(hipMemcpyAsync(*b.p, b.host, b.bytes, hipMemcpyHostToDevice, st_));
+    }
+    return MBLS_SUCCESS;
+}
+
+eIcicleError Staging::close(bool is_async) {
+    bool host_out = false;
+    for (int i = 0; i < n_; ++i) {
+        const Block& b = blocks_[i];
+        if (b.kind != OUT) continue;
+        MBLS_TRY(hipMemcpyAsync(b.host, *b.p, b.bytes, hipMemcpyDeviceToHost, st_));
+        host_out = true;
+    }
+    if (!is_async || host_out) MBLS_TRY(hipStreamSynchronize(st_));
+    return MBLS_SUCCESS;
+}
+
 // ---- per-device pool of scratch contexts ------------------------------------------------
 // Lease policy (CtxLease): among the free contexts of the current device take, in order,
 //   1. one whose last call was on this same stream (preferred: stream order usually serialises it);

@@ -8,6 +8,7 @@
 #include <stdlib.h>
 
 #include <mutex>
+#include <optional>
 #include <unordered_map>
 #include <vector>
 
@@ -107,6 +108,50 @@ void count_scratch_free(size_t bytes);
 // Reserve-then-take helper: computes the total of a list of sizes first, so the arena
 // reallocates at most once per call (before any kernel of this call is enqueued).
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+// Operand staging of one call on stream `st`.  The call declares its arena blocks in order --
+// scratch(), in(), out() -- then open()s: one lease, ONE reserve of the declared sum, the blocks
+// handed out in declaration order (into *p), the host inputs copied in.  A device operand is
+// passed through (*p = the caller's pointer, no block).  close() copies the host outputs back and
+// synchronises unless the call is async with every output on the device.  The Staging object holds
+// the lease: it lives until the call's last enqueue.
+class Staging {
+  public:
+    // LEASE_IF_STAGED: a call with nothing to stage takes no context, so it records no `done`
+    // event (an event marker holds the next dispatch ~5 us)
+    enum LeaseRule { LEASE_ALWAYS, LEASE_IF_STAGED };
+    Staging(hipStream_t st, LeaseRule rule) : st_(st), always_(rule == LEASE_ALWAYS) {}
+    void scratch(uint8_t** p, size_t bytes) { add(p, nullptr, bytes, SCRATCH); }
+    void in(const uint8_t** p, const void* src, size_t bytes, bool on_device) {
+        if (on_device) *p = static_cast<const uint8_t*>(src);
+        else add(const_cast<uint8_t**>(p), const_cast<void*>(src), bytes, IN);
+    }
+    void out(uint8_t** p, void* dst, size_t bytes, bool on_device) {
+        if (on_device) *p = static_cast<uint8_t*>(dst);
+        else add(p, dst, bytes, OUT);
+    }
+    eIcicleError open();
+    eIcicleError close(bool is_async);
+
+  private:
+    enum Kind { SCRATCH, IN, OUT };
+    struct Block {
+        uint8_t** p;
+        void* host;
+        size_t bytes;
+        Kind kind;
+    };
+    static constexpr int MAX_BLOCKS = 6;
+    void add(uint8_t** p, void* host, size_t bytes, Kind kind) {
+        if (n_ < MAX_BLOCKS) blocks_[n_] = {p, host, bytes, kind};
+        ++n_;  // beyond MAX_BLOCKS: open() fails
+    }
+    hipStream_t st_;
+    bool always_;
+    Block blocks_[MAX_BLOCKS];
+    int n_ = 0;
+    std::optional<CtxLease> lease_;
+};
 
 // is `p` a device (or managed) pointer?  Used only for defensive validation.
 bool is_device_pointer(const void* p);

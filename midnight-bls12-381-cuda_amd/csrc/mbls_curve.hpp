@@ -225,6 +225,12 @@ struct FieldIO<PFq2> {
     MBLS_DEV static void st(uint8_t* p, const PFq2& v) { store<FqCfg>(p + (pairdpp::odd() ? 48 : 0), v.v); }
 };
 
+// point record sizes (host and device): affine (x, y) 96 / 192 bytes, Jacobian (X, Y, Z) 144 / 288
+template <class F>
+struct PointSize {
+    static constexpr size_t AFF = 2 * FieldIO<F>::BYTES, JAC = 3 * FieldIO<F>::BYTES;
+};
+
 // element type of the one-chain-per-thread ("lane") kernels: G1 uses Fq in one lane, G2 the
 // pair-sliced Fq2 in two lanes (mbls_pairfield.hpp)
 template <class F>

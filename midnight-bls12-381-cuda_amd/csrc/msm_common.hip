@@ -1958,7 +1958,7 @@ eIcicleError multi_device_res(int dev, MultiDevRes*& out) {
     MBLS_TRY(hipGetDevice(&cur));
     MBLS_TRY(hipSetDevice(dev));
     MultiDevRes r;
-    constexpr size_t JAC = GroupTraits<Fq2>::JAC;  // the larger point
+    constexpr size_t JAC = PointSize<Fq2>::JAC;  // the larger point
     hipError_t e = hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking);
     for (int k = 0; k < MAX_SHARDS && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&r.ev[k], hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&r.done, hipEventDisableTiming);

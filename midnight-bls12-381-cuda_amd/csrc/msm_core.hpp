@@ -5,7 +5,8 @@
 // (:748-781), accumulation (:269-366), bucket reduction (:376-513), final (:529-596);
 // boundary msm_cuda_impl / msm_g2_cuda_impl (icicle_curve_api.cu:243-618).
 //
-// Pipeline (all on the caller's stream, scratch from the per-stream arena):
+// Pipeline (all on the caller's stream; scratch: one region of the leased arena, laid out by
+// msm_scratch below -- the one list of its blocks, used both to size and to carve it):
 //   1-3. sort (msm_common.hip): signed c-bit digits of each scalar (Montgomery -> standard if
 //                     flagged, endomorphism split), contributions (index|sign) sorted by bucket.
 //                     c <= 16 (default): the partitioned counting sort, k_digits_part +
@@ -215,23 +216,13 @@ eIcicleError launch_part_sort(const MsmPlan& P, const uint32_t* ent, const uint3
 // a chunk partial's bytes: the accumulator's raw radix-2^28 XYZZ limbs (4 x 14 words, per Fq2
 // component for G2): no to_words conversion at the flush, which is divergent -- a bucket boundary
 // falls inside ~25% of the chunks, at a different step in every lane -- and no unpack_shift8 when
-// the bucket sums read them
-template <class F>
-struct PartialBytes;
-template <>
-struct PartialBytes<Fq> {
-    static constexpr size_t value = 224;
-};
-template <>
-struct PartialBytes<Fq2> {
-    static constexpr size_t value = 448;
-};
-// with a lane-mode level 0 (every large MSM) k_bucket_small stores the bucket sums as raw XYZZ
+// the bucket sums read them.
+// With a lane-mode level 0 (every large MSM) k_bucket_small stores the bucket sums as raw XYZZ
 // limbs too (store_xyzz28 / store_xyzz28p) and level 0 adds them in XYZZ (k_reduce_scaled_r28x /
 // _r28px): no x_to_jac per bucket, add-2008-s instead of add-2007-bl in the level's chains, no
 // unpack_shift8 on its loads
 template <class F>
-constexpr size_t xyzz_bucket_bytes() {
+constexpr size_t xyzz_bytes() {  // a raw XYZZ record: chunk partial, bucket sum, G2 lane-level output
     return std::is_same<F, Fq>::value ? 224 : 448;
 }
 MBLS_DEV void store_xyzz28(uint8_t* __restrict__ partials, uint32_t seg, const r28::X28& acc) {
@@ -1379,28 +1370,17 @@ __global__ __launch_bounds__(128) void k_precompute(const uint8_t* in, uint8_t* 
 // ------------------------------------------------------------------------------------
 // host orchestration
 // ------------------------------------------------------------------------------------
-template <class F>
-struct GroupTraits;
-template <>
-struct GroupTraits<Fq> {
-    static constexpr size_t AFF = 96, JAC = 144;
-};
-template <>
-struct GroupTraits<Fq2> {
-    static constexpr size_t AFF = 192, JAC = 288;
-};
-
-struct MsmScratchSizes {
-    size_t dsrc, keys, vals, ranks, sorted, words, tmp, owner, first, partials, buckets, levelT, levelR, windows, phi;
-    size_t ent, segtab, parts;  // partitioned sort (keys / vals / ranks are 0 then)
-    size_t order, perm;         // k_bucket_order: bin histograms / their scan, bucket permutation
-    size_t heavy, hslices, hres;  // HeavyTab: per-entry words (x4), per-slice owner words, slice sums
-    size_t phelp;                 // PartHelp: hh + hpart (help shares the second `parts` array)
-    size_t gdone = align_up(HEAVY_GDONE * 4);
-    size_t total() const {
-        return dsrc + keys + vals + ranks + sorted + 4 * words + tmp + owner + first + partials + buckets + levelT + levelR +
-               windows + phi + ent + 2 * segtab + 2 * parts + 2 * order + perm + 4 * heavy + hslices + hres + phelp + gdone;
-    }
+// the scratch blocks of one MSM, in arena order; msm_scratch below is their one description
+struct MsmScratch {
+    uint32_t *keys, *vals, *ranks;  // tiled sort (zero bytes with the partitioned sort)
+    uint8_t* dsrc;
+    uint32_t *sorted, *counts, *offsets, *nchunks, *chunk_off, *tmp, *owner, *first;
+    uint8_t *partials, *buckets, *levelT, *levelR, *windows;
+    uint8_t* phi;                                  // the per-call image table, or null
+    uint32_t *ent, *seg_off, *seg_cnt, *part_tot;  // partitioned sort (zero bytes with the tiled sort)
+    PartHelp ph;
+    uint32_t *binhist, *binbase, *perm;  // k_bucket_order: bin histograms, their scan, bucket permutation
+    HeavyTab H;
 };
 
 // reduction levels with fewer segments than this run one segment per wave (-DMBLS_WAVE_MIN tunes;
@@ -1418,6 +1398,8 @@ struct MsmScratchSizes {
 #endif
 inline uint32_t wave_min_chains(bool fq2 = false) { return fq2 ? MBLS_WAVE_MIN_G2 : MBLS_WAVE_MIN; }
 
+// the endomorphism images of the bases are built per call (msm_device's `phi` block)
+inline bool msm_image_table(const MsmPlan& P) { return P.split > 1 && !P.prepared; }
 // raw XYZZ buckets for this plan (level 0 in lanes)
 template <class F>
 inline bool buckets_xyzz(const MsmPlan& P) {
@@ -1428,63 +1410,81 @@ inline bool buckets_xyzz(const MsmPlan& P) {
 template <class F>
 inline size_t level_bytes(const MsmPlan& P) {
     return (std::is_same<F, Fq2>::value && buckets_xyzz<F>(P) && P.levels > 1 && P.mode[1] == MODE_LANE)
-               ? xyzz_bucket_bytes<F>()
-               : GroupTraits<F>::JAC;
+               ? xyzz_bytes<F>()
+               : PointSize<F>::JAC;
 }
+// The one description of an MSM's scratch region: every block in arena order, its bytes and the
+// pointer it becomes.  With `base` it carves the region into S; without (the counting pass) S's
+// pointers are null.  Either way it returns the region's bytes (a sum of 256-byte multiples).
 template <class F>
-inline MsmScratchSizes msm_scratch_sizes(const MsmPlan& P) {
-    constexpr size_t jac = GroupTraits<F>::JAC, aff = GroupTraits<F>::AFF;
-    // the chunk count is data dependent (a short last chunk per bucket): its bound
-    const uint32_t max_chunks = (uint32_t)(P.contributions / P.chunk + P.TB + 1);
-    const size_t part = PartialBytes<F>::value;                                // a chunk partial's bytes
-    const size_t bkt = buckets_xyzz<F>(P) ? xyzz_bucket_bytes<F>() : jac;  // a bucket sum's bytes
-    const size_t lvl = level_bytes<F>(P);                                      // a level record's bytes
-    MsmScratchSizes z;
-    // the per-call image table; with bstride > 1 also the compact copy of the points (2n rows)
-    z.phi = P.split > 1 && !P.prepared ? align_up(P.pts / P.split * (P.split - 1 + (P.bstride > 1 ? 1 : 0)) * aff) : 0;
+inline size_t msm_scratch(const MsmPlan& P, uint8_t* base, MsmScratch& S) {
+    constexpr size_t jac = PointSize<F>::JAC, aff = PointSize<F>::AFF;
+    size_t used = 0;
+    auto take = [&](auto*& p, size_t bytes) {
+        p = base ? reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + used) : nullptr;
+        used += align_up(bytes);
+    };
+    const bool psort = partition_sort(P);
+    const PartSortSizes ps = psort ? part_sort_sizes(P) : PartSortSizes();  // zero bytes each
     const size_t NC = P.contributions;
-    if (partition_sort(P)) {
-        const PartSortSizes s = part_sort_sizes(P);
-        z.keys = z.vals = z.ranks = 0;
-        z.ent = align_up(s.ent);
-        z.segtab = align_up(s.segtab);
-        z.parts = align_up(s.parts);
-        z.phelp = align_up((size_t)PH_HELPERS * 129 * 4);
-    } else {
-        z.phelp = 0;
-        z.keys = align_up(NC * 4);
-        z.vals = align_up(NC * 4);
-        z.ranks = align_up(NC * 4);
-        z.ent = z.segtab = z.parts = 0;
-    }
-    z.dsrc = align_up(digits_src_bytes((uint32_t)(P.split > 1 ? P.pts / P.split : P.pts / P.F), P.split));
-    z.sorted = align_up(NC * 4);
-    z.words = align_up(((size_t)P.TB + 4) * 4);  // + the maximum and the HeavyTab counters
+    // the chunk count is data dependent (a short last chunk per bucket): its bound
+    const uint32_t max_chunks = (uint32_t)(NC / P.chunk + P.TB + 1);
+    take(S.keys, 4 * (psort ? 0 : NC));
+    take(S.vals, 4 * (psort ? 0 : NC));
+    take(S.ranks, 4 * (psort ? 0 : NC));
+    take(S.dsrc, digits_src_bytes((uint32_t)(P.split > 1 ? P.pts / P.split : P.pts / P.F), P.split));
+    take(S.sorted, 4 * NC);
+    const size_t tb_words = (size_t)P.TB + 4;  // + the maximum and the HeavyTab counters
+    take(S.counts, 4 * tb_words);
+    take(S.offsets, 4 * tb_words);
+    take(S.nchunks, 4 * tb_words);
+    take(S.chunk_off, 4 * tb_words);
+    // + the chunk-count block totals and their prefixes (k_chunk_counts / k_scan_small)
+    take(S.tmp,
+         4 * (scan_tmp_words(std::max(std::max(max_chunks, P.TB), order_words(P.TB))) + 2 * ((size_t)P.TB / 128 + 2)));
+    take(S.owner, 4 * (size_t)max_chunks);
+    take(S.first, 4 * (NC / P.chunk + 2));
+    take(S.partials, (size_t)max_chunks * xyzz_bytes<F>());
+    take(S.buckets, (size_t)P.TB * (buckets_xyzz<F>(P) ? xyzz_bytes<F>() : jac));
+    // V / U ping-pong halves sized for the widest level's outputs (k_reduce_scaled)
+    const size_t mo0 = P.levels ? (P.level_m[0] + P.seg(0) - 1) / P.seg(0) : 1;
+    take(S.levelT, 2 * mo0 * P.Wg * level_bytes<F>(P));
+    take(S.levelR, 2 * mo0 * P.Wg * level_bytes<F>(P));
+    take(S.windows, (size_t)P.Wg * jac);
+    // the per-call image table; with bstride > 1 also the compact copy of the points (2n rows)
+    S.phi = nullptr;
+    if (msm_image_table(P)) take(S.phi, P.pts / P.split * (P.split - 1 + (P.bstride > 1 ? 1 : 0)) * aff);
+    take(S.ent, ps.ent);
+    take(S.seg_off, ps.segtab);
+    take(S.seg_cnt, ps.segtab);
+    take(S.part_tot, ps.parts);
+    take(S.ph.help, ps.parts);
+    take(S.ph.hh, 4 * (psort ? (size_t)PH_HELPERS * 129 : 0));  // hh[PH_HELPERS][128], then hpart[PH_HELPERS]
+    S.ph.hpart = S.ph.hh ? S.ph.hh + (size_t)PH_HELPERS * 128 : nullptr;
+    take(S.binhist, 4 * ((size_t)order_words(P.TB) + 1));
+    take(S.binbase, 4 * ((size_t)order_words(P.TB) + 1));
+    take(S.perm, 4 * (size_t)P.TB);
     // heavy buckets have > SMALL_MAX partials: at most max_chunks / (SMALL_MAX + 1) of them, and
     // at most max_chunks / HEAVY_SLICE + (heavy buckets) slices
     const size_t max_heavy = std::min<size_t>(P.TB, max_chunks / (SMALL_MAX + 1) + 1);
     const size_t max_slices = max_chunks / HEAVY_SLICE + max_heavy + 1;
-    z.heavy = align_up(max_heavy * 4);
-    z.hslices = align_up(max_slices * 4);
+    take(S.H.bucket, 4 * max_heavy);
+    take(S.H.first, 4 * max_heavy);
+    take(S.H.nslices, 4 * max_heavy);
+    take(S.H.done, 4 * max_heavy);
+    take(S.H.owner, 4 * max_slices);
     // slice sums: the planned slices (>= HEAVY_SLICE_MIN partials, <= HEAVY_LDS buckets) or the
     // fixed plan's
-    z.hres = align_up(std::max(max_slices, max_chunks / HEAVY_SLICE_MIN + std::min<size_t>(max_heavy, HEAVY_LDS) + 1) * jac);
-    z.order = align_up(((size_t)order_words(P.TB) + 1) * 4);
-    z.perm = align_up((size_t)P.TB * 4);
-    // + the chunk-count block totals and their prefixes (k_chunk_counts / k_scan_small)
-    z.tmp = align_up((scan_tmp_words(std::max(std::max(max_chunks, P.TB), order_words(P.TB))) +
-                      2 * ((size_t)P.TB / 128 + 2)) *
-                     4);
-    z.owner = align_up((size_t)max_chunks * 4);
-    z.first = align_up((NC / P.chunk + 2) * 4);
-    z.partials = align_up((size_t)max_chunks * part);
-    z.buckets = align_up((size_t)P.TB * bkt);
-    // V / U ping-pong halves sized for the widest level's outputs (k_reduce_scaled)
-    const size_t mo0 = P.levels ? (P.level_m[0] + P.seg(0) - 1) / P.seg(0) : 1;
-    z.levelT = align_up(2 * mo0 * P.Wg * lvl);
-    z.levelR = align_up(2 * mo0 * P.Wg * lvl);
-    z.windows = align_up((size_t)P.Wg * jac);
-    return z;
+    take(S.H.res,
+         std::max(max_slices, max_chunks / HEAVY_SLICE_MIN + std::min<size_t>(max_heavy, HEAVY_LDS) + 1) * jac);
+    take(S.H.gdone, 4 * (size_t)HEAVY_GDONE);
+    S.H.cnt = base ? S.nchunks + P.TB + 1 : nullptr;  // words TB + 1, TB + 2 of the chunk-count array
+    return used;
+}
+template <class F>
+inline size_t msm_scratch_bytes(const MsmPlan& P) {
+    MsmScratch counted;
+    return msm_scratch<F>(P, nullptr, counted);
 }
 
 inline bool debug_enabled() {
@@ -1590,7 +1590,7 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
                         uint8_t* icicle_out = nullptr, const TailPipe* pipe = nullptr,
                         hipEvent_t acc_event = nullptr) {
     Arena& arena = ctx.arena;
-    constexpr size_t AFF = GroupTraits<F>::AFF;
+    constexpr size_t AFF = PointSize<F>::AFF;
     constexpr uint32_t LN = LaneOf<F>::LANES;  // lanes per chain in the lane-mode kernels
     // mbls_msm_accumulate_event: recorded after the accumulation launch below, or wherever this
     // function returns before it (an empty MSM, an error)
@@ -1604,48 +1604,11 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
     const uint32_t TB = P.TB;
     const size_t NC = P.contributions;
     const bool xb = buckets_xyzz<F>(P);
-    const MsmScratchSizes z = msm_scratch_sizes<F>(P);
-    uint32_t* keys = (uint32_t*)arena.take(z.keys);
-    uint32_t* vals = (uint32_t*)arena.take(z.vals);
-    uint32_t* ranks = (uint32_t*)arena.take(z.ranks);
-    uint8_t* dsrc = (uint8_t*)arena.take(z.dsrc);
-    uint32_t* sorted = (uint32_t*)arena.take(z.sorted);
-    uint32_t* counts = (uint32_t*)arena.take(z.words);
-    uint32_t* offsets = (uint32_t*)arena.take(z.words);
-    uint32_t* nchunks = (uint32_t*)arena.take(z.words);
-    uint32_t* chunk_off = (uint32_t*)arena.take(z.words);
-    uint32_t* tmp = (uint32_t*)arena.take(z.tmp);
-    uint32_t* owner = (uint32_t*)arena.take(z.owner);
-    uint32_t* first = (uint32_t*)arena.take(z.first);
-    uint8_t* partials = (uint8_t*)arena.take(z.partials);
-    uint8_t* buckets = (uint8_t*)arena.take(z.buckets);
-    uint8_t* levelT = (uint8_t*)arena.take(z.levelT);
-    uint8_t* levelR = (uint8_t*)arena.take(z.levelR);
-    uint8_t* windows = (uint8_t*)arena.take(z.windows);
-    const bool img_table = P.split > 1 && !P.prepared;  // the images are built per call
-    uint8_t* phi = img_table ? (uint8_t*)arena.take(z.phi) : nullptr;
-    const bool psort = partition_sort(P);
-    uint32_t* ent = (uint32_t*)arena.take(z.ent);
-    uint32_t* seg_off = (uint32_t*)arena.take(z.segtab);
-    uint32_t* seg_cnt = (uint32_t*)arena.take(z.segtab);
-    uint32_t* part_tot = (uint32_t*)arena.take(z.parts);
-    PartHelp ph;
-    ph.help = (uint32_t*)arena.take(z.parts);
-    ph.hh = (uint32_t*)arena.take(z.phelp);
-    ph.hpart = ph.hh ? ph.hh + (size_t)PH_HELPERS * 128 : nullptr;
-    uint32_t* binhist = (uint32_t*)arena.take(z.order);
-    uint32_t* binbase = (uint32_t*)arena.take(z.order);
-    uint32_t* perm = (uint32_t*)arena.take(z.perm);
-    HeavyTab H;
-    H.bucket = (uint32_t*)arena.take(z.heavy);
-    H.first = (uint32_t*)arena.take(z.heavy);
-    H.nslices = (uint32_t*)arena.take(z.heavy);
-    H.done = (uint32_t*)arena.take(z.heavy);
-    H.owner = (uint32_t*)arena.take(z.hslices);
-    H.res = (uint8_t*)arena.take(z.hres);
-    H.gdone = (uint32_t*)arena.take(z.gdone);
-    H.cnt = nchunks + TB + 1;
-    if (!H.gdone || !H.res || !windows || (img_table && !phi) || (psort && !ph.hh)) return MBLS_ALLOCATION_FAILED;
+    const bool img_table = msm_image_table(P), psort = partition_sort(P);
+    MsmScratch S;
+    uint8_t* region = static_cast<uint8_t*>(arena.take(msm_scratch_bytes<F>(P)));
+    if (!region) return MBLS_ALLOCATION_FAILED;
+    msm_scratch<F>(P, region, S);
 
     ProfScope prof_all("msm.total", st);
     eIcicleError er;
@@ -1666,7 +1629,7 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
         ctx.forked = true;
         MBLS_TRY(hipEventRecord(ev[0], st));
         MBLS_TRY(hipStreamWaitEvent(side, ev[0], 0));
-        er = P.split == 2 ? launch_glv_table(bases, phi, n, side) : launch_psi_table(bases, phi, n, side);
+        er = P.split == 2 ? launch_glv_table(bases, S.phi, n, side) : launch_psi_table(bases, S.phi, n, side);
         if (er != MBLS_SUCCESS) return er;
         MBLS_TRY(hipEventRecord(ev[1], side));
     }
@@ -1677,12 +1640,12 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
     {
         ProfScope ps("msm.digits", st);
         if (psort) {
-            er = launch_digits_part(scalars, scalars_mont, n, P, ent, seg_off, seg_cnt, part_tot, dsrc, nchunks + TB, st,
-                                    fused_table ? bases : nullptr, fused_table ? phi : nullptr,
-                                    fused_cc ? binhist : nullptr, fused_cc ? order_words(TB) : 0u);
+            er = launch_digits_part(scalars, scalars_mont, n, P, S.ent, S.seg_off, S.seg_cnt, S.part_tot, S.dsrc,
+                                    S.nchunks + TB, st, fused_table ? bases : nullptr, fused_table ? S.phi : nullptr,
+                                    fused_cc ? S.binhist : nullptr, fused_cc ? order_words(TB) : 0u);
         } else {
-            MBLS_TRY(hipMemsetAsync(counts, 0, (size_t)TB * 4, st));
-            er = launch_digits(scalars, scalars_mont, n, P, keys, vals, ranks, counts, dsrc, st);
+            MBLS_TRY(hipMemsetAsync(S.counts, 0, (size_t)TB * 4, st));
+            er = launch_digits(scalars, scalars_mont, n, P, S.keys, S.vals, S.ranks, S.counts, S.dsrc, st);
         }
         if (er != MBLS_SUCCESS) return er;
     }
@@ -1691,32 +1654,33 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
         // chunk_off = exclusive scan of the chunk counts, spread over the kernels below: block
         // prefixes in k_chunk_counts or k_part_sort (written over `counts`, no longer needed), the
         // block totals scanned beside the order histograms, the sum in k_chunk_owner
-        uint32_t* cloc = counts;
+        uint32_t* cloc = S.counts;
         const uint32_t nblk = (TB + (1u << cs) - 1) >> cs;
-        uint32_t* blk_tot = tmp;
-        uint32_t* blk_pre = tmp + (nblk + 2);
+        uint32_t* blk_tot = S.tmp;
+        uint32_t* blk_pre = S.tmp + (nblk + 2);
         if (psort) {  // writes counts (or with fused_cc the chunk counts), offsets (incl. offsets[TB]) and sorted
             ChunkCountOut cc;
             if (fused_cc) {
-                cc.nchunks = nchunks;
-                cc.binhist = binhist;
+                cc.nchunks = S.nchunks;
+                cc.binhist = S.binhist;
                 cc.blk_tot = blk_tot;
                 cc.L = P.chunk;
                 cc.m = TB;
             }
-            er = launch_part_sort(P, ent, seg_off, seg_cnt, part_tot, counts, offsets, sorted, cc, st, ph);
+            er = launch_part_sort(P, S.ent, S.seg_off, S.seg_cnt, S.part_tot, S.counts, S.offsets, S.sorted, cc, st,
+                                  S.ph);
             if (er != MBLS_SUCCESS) return er;
-        } else if ((er = scan_exclusive(counts, offsets, TB, tmp, st)) != MBLS_SUCCESS) {
+        } else if ((er = scan_exclusive(S.counts, S.offsets, TB, S.tmp, st)) != MBLS_SUCCESS) {
             return er;
         }
-        if (!fused_cc &&
-            (er = launch_chunk_counts(counts, offsets, nchunks, TB, P.chunk, binhist, 1u, psort, cloc, blk_tot, st)) !=
-                MBLS_SUCCESS)
+        if (!fused_cc && (er = launch_chunk_counts(S.counts, S.offsets, S.nchunks, TB, P.chunk, S.binhist, 1u, psort,
+                                                   cloc, blk_tot, st)) != MBLS_SUCCESS)
             return er;
-        if ((er = launch_order_scan(binhist, binbase, TB, blk_tot, blk_pre, nblk, st)) != MBLS_SUCCESS) return er;
-        if (!psort && (er = launch_scatter(keys, vals, ranks, NC, offsets, sorted, st)) != MBLS_SUCCESS) return er;
-        if ((er = launch_chunk_owner(cloc, blk_pre, cs, chunk_off, offsets, TB, P.chunk, owner, first, nchunks, binbase,
-                                     perm, H, st)) != MBLS_SUCCESS)
+        if ((er = launch_order_scan(S.binhist, S.binbase, TB, blk_tot, blk_pre, nblk, st)) != MBLS_SUCCESS) return er;
+        if (!psort && (er = launch_scatter(S.keys, S.vals, S.ranks, NC, S.offsets, S.sorted, st)) != MBLS_SUCCESS)
+            return er;
+        if ((er = launch_chunk_owner(cloc, blk_pre, cs, S.chunk_off, S.offsets, TB, P.chunk, S.owner, S.first, S.nchunks,
+                                     S.binbase, S.perm, S.H, st)) != MBLS_SUCCESS)
             return er;
     }
     if (st != main_st) {  // join: the accumulation waits for the front
@@ -1731,10 +1695,10 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
         if (img_table && !fused_table) MBLS_TRY(hipStreamWaitEvent(st, ev[1], 0));
         const uint32_t threads = (uint32_t)((NC + P.chunk - 1) / P.chunk) * LN;
         // bstride > 1: the split kernel wrote [P; phi P] into `phi` (compact slot-0 copy)
-        const uint8_t* acc_b = P.bstride > 1 ? phi : bases;
-        const uint8_t* acc_phi = P.bstride > 1 ? phi + (size_t)n * AFF : phi;
-        hipLaunchKernelGGL(accumulate_kernel<F>(), dim3((threads + 255) / 256), dim3(256), 0, st, sorted, offsets,
-                           chunk_off, first, 0u, TB, acc_b, acc_phi, nsplit, P.chunk, partials);
+        const uint8_t* acc_b = P.bstride > 1 ? S.phi : bases;
+        const uint8_t* acc_phi = P.bstride > 1 ? S.phi + (size_t)n * AFF : S.phi;
+        hipLaunchKernelGGL(accumulate_kernel<F>(), dim3((threads + 255) / 256), dim3(256), 0, st, S.sorted, S.offsets,
+                           S.chunk_off, S.first, 0u, TB, acc_b, acc_phi, nsplit, P.chunk, S.partials);
     }
     // mbls_msm_accumulate_event: the tail starts here (the caller passes it to the last member)
     if (hipEvent_t e = acc_ev.release()) MBLS_TRY(hipEventRecord(e, st));
@@ -1745,8 +1709,8 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
         // in-line empty passes ~6 us per launch (round 3 timelines)
         const uint32_t light_blocks = (TB * LN + 255) / 256;
         if (pipe && pipe->reuse) MBLS_TRY(hipStreamWaitEvent(st, pipe->reuse, 0));
-        hipLaunchKernelGGL(k_bucket_small<F>, dim3(light_blocks + HEAVY_BLOCKS), dim3(256), 0, st, chunk_off, perm, binbase,
-                           order_words(TB), partials, buckets, light_blocks, H, xb ? 1 : 0);
+        hipLaunchKernelGGL(k_bucket_small<F>, dim3(light_blocks + HEAVY_BLOCKS), dim3(256), 0, st, S.chunk_off, S.perm,
+                           S.binbase, order_words(TB), S.partials, S.buckets, light_blocks, S.H, xb ? 1 : 0);
     }
     if (pipe) {  // the tail moves to the side stream
         MBLS_TRY(hipEventRecord(pipe->bucket_done, st));
@@ -1758,9 +1722,9 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
         // scaled running-sum levels (k_reduce_scaled): V / U ping-pong in levelR / levelT, the
         // last level writes the window sums straight into `windows`
         const size_t half = ((P.level_m[0] + P.seg(0) - 1) / P.seg(0)) * (size_t)P.Wg * level_bytes<F>(P);
-        uint8_t* vb[2] = {levelR, levelR + half};
-        uint8_t* ub[2] = {levelT, levelT + half};
-        const uint8_t* V = buckets;
+        uint8_t* vb[2] = {S.levelR, S.levelR + half};
+        uint8_t* ub[2] = {S.levelT, S.levelT + half};
+        const uint8_t* V = S.buckets;
         const uint8_t* U = nullptr;
         bool raw_in = xb;  // level l's inputs are raw XYZZ records
         for (int l = 0; l < P.levels; ++l) {
@@ -1768,7 +1732,7 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
             const uint32_t m_out = (m_in + P.seg(l) - 1) / P.seg(l);
             const bool last = l == P.levels - 1;
             uint8_t* Vo = last ? nullptr : vb[l & 1];
-            uint8_t* Uo = last ? windows : ub[l & 1];
+            uint8_t* Uo = last ? S.windows : ub[l & 1];
             const uint32_t chains = m_out * (uint32_t)P.Wg;
             if (!raw_in) {
                 launch_reduce_scaled<F>(P.mode[l], V, U, m_in, P.seg_log[l], P.Wg, l == 0 ? 1 : 0, Vo, Uo, chains, st);
@@ -1789,9 +1753,9 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
     {
         ProfScope ps("msm.final", st);
         if (icicle_out)
-            hipLaunchKernelGGL(k_final_icicle<F>, dim3(1), dim3(64), 0, st, windows, P.Wg, P.c, icicle_out);
+            hipLaunchKernelGGL(k_final_icicle<F>, dim3(1), dim3(64), 0, st, S.windows, P.Wg, P.c, icicle_out);
         else
-            hipLaunchKernelGGL(k_final<F>, dim3(1), dim3(64), 0, st, windows, P.Wg, P.c, result);
+            hipLaunchKernelGGL(k_final<F>, dim3(1), dim3(64), 0, st, S.windows, P.Wg, P.c, result);
     }
     MBLS_TRY(hipGetLastError());
     return MBLS_SUCCESS;
@@ -1811,7 +1775,7 @@ template <class F>
 eIcicleError msm_call(const void* scalars, const void* bases, int msm_size, const MSMConfig* cfg, void* results,
                       int entry) {
     const bool icicle_semantics = entry != MSM_RAW;
-    constexpr size_t AFF = GroupTraits<F>::AFF, JAC = GroupTraits<F>::JAC;
+    constexpr size_t AFF = PointSize<F>::AFF, JAC = PointSize<F>::JAC;
     if (!cfg || !results) return MBLS_INVALID_POINTER;
     hipStream_t st = static_cast<hipStream_t>(cfg->stream);
     // a pending mbls_msm_accumulate_event belongs to this call whatever happens below: the last
@@ -1832,7 +1796,7 @@ eIcicleError msm_call(const void* scalars, const void* bases, int msm_size, cons
     if (cfg->precompute_factor > 1 && cfg->are_points_on_device && bases && msm_size > 0) {
         const bool sh = cfg->are_points_shared_in_batch || batch == 1;
         const size_t want = (size_t)msm_size * (size_t)cfg->precompute_factor * (sh ? 1 : (size_t)batch) *
-                            GroupTraits<F>::AFF;
+                            AFF;
         if (precompute_strict() ? !precompute_is_table(bases, cfg->precompute_factor, want)
                                 : device_bytes_from(bases) < want) {
             cfg_plain = *cfg;
@@ -1863,7 +1827,7 @@ eIcicleError msm_call(const void* scalars, const void* bases, int msm_size, cons
     if (debug_enabled())
         fprintf(stderr, "[mbls] msm n=%d c=%d W=%d Wg=%d split=%d TB=%u contributions=%zu chunk=%u levels=%d\n", msm_size,
                 P.c, P.W, P.Wg, P.split, P.TB, P.contributions, P.chunk, P.levels);
-    const size_t scratch = msm_scratch_sizes<F>(P).total();
+    const size_t scratch = msm_scratch_bytes<F>(P);
     const bool piped = batch > 1 && batch_pipe() > 0;
     er = lease.reserve(st_s + st_b + st_r + scratch * (piped ? 2 : 1) + 4096);
     if (er != MBLS_SUCCESS) return er;
@@ -1985,7 +1949,7 @@ eIcicleError enable_peer(int from, int to);
 template <class F>
 eIcicleError msm_multi_device(const void* scalars, const void* const* bases_per_dev, const int* devs, int ndev,
                               int msm_size, const MSMConfig* cfg, void* result) {
-    constexpr size_t JAC = GroupTraits<F>::JAC;
+    constexpr size_t JAC = PointSize<F>::JAC;
     if (!cfg || !result || !devs || !bases_per_dev) return MBLS_INVALID_POINTER;
     if (ndev < 1 || ndev > MAX_SHARDS || msm_size < 0 || msm_size > (1 << MAX_MSM_LOG)) return MBLS_INVALID_ARGUMENT;
     if (cfg->batch_size > 1 || cfg->precompute_factor > 1) return MBLS_INVALID_ARGUMENT;
@@ -2073,7 +2037,7 @@ eIcicleError msm_multi_device(const void* scalars, const void* const* bases_per_
 // Montgomery affine; standard-form input (are_points_montgomery_form = false) is converted.
 template <class F>
 eIcicleError precompute_call(const void* in, int n, const MSMConfig* cfg, void* out) {
-    constexpr size_t AFF = GroupTraits<F>::AFF;
+    constexpr size_t AFF = PointSize<F>::AFF;
     if (!cfg || !in || !out) return MBLS_INVALID_POINTER;
     if (n < 0) return MBLS_INVALID_ARGUMENT;
     const int factor = cfg->precompute_factor > 0 ? cfg->precompute_factor : 1;

@@ -31,7 +31,6 @@
 
 #include <memory>
 #include <mutex>
-#include <optional>
 #include <vector>
 
 #include "mbls_common.hpp"
@@ -676,35 +675,21 @@ eIcicleError ntt_call(const mbls_fr_t* input, int size, NTTDir dir, const NTTCon
     const bool same = in_dev && out_dev && input == output;
     const bool work_in_tmp = perm_in || (coset && !inverse) || (same && !perm_out);
 
-    size_t need = 0;
-    if (!in_dev) need += align_up(bytes);
-    if (!out_dev) need += align_up(bytes);
-    if (work_in_tmp) need += align_up(bytes);
-    if (perm_out) need += align_up(bytes);
     // a transform that needs no staging (device in / out, natural order, distinct buffers: the
-    // prover's shape) takes no scratch context, so it records no `done` event: an event marker
-    // holds the next dispatch ~5 us, 1% of a 2^22 transform
-    std::optional<CtxLease> lease;
-    Arena* arena = nullptr;
-    eIcicleError er = MBLS_SUCCESS;
-    if (need) {
-        lease.emplace(st);
-        if (!*lease) return lease->error();
-        if ((er = lease->reserve(need)) != MBLS_SUCCESS) return er;
-        arena = &(**lease).arena;
-    }
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(input);
-    uint8_t* dst = reinterpret_cast<uint8_t*>(output);
-    if (!in_dev) {
-        void* t = arena->take(bytes);
-        MBLS_TRY(hipMemcpyAsync(t, input, bytes, hipMemcpyHostToDevice, st));
-        src = static_cast<const uint8_t*>(t);
-    }
-    if (!out_dev) dst = static_cast<uint8_t*>(arena->take(bytes));
-    uint8_t* wout = perm_out ? static_cast<uint8_t*>(arena->take(bytes)) : dst;
+    // prover's shape) takes no scratch context (Staging::LEASE_IF_STAGED): the lease's `done`
+    // event would hold the next dispatch ~5 us, 1% of a 2^22 transform
+    Staging S(st, Staging::LEASE_IF_STAGED);
+    const uint8_t* src;
+    uint8_t *dst, *wout = nullptr, *t = nullptr;
+    S.in(&src, input, bytes, in_dev);
+    S.out(&dst, output, bytes, out_dev);
+    if (perm_out) S.scratch(&wout, bytes);
+    if (work_in_tmp) S.scratch(&t, bytes);
+    eIcicleError er = S.open();
+    if (er != MBLS_SUCCESS) return er;
+    if (!perm_out) wout = dst;
     const uint8_t* win = src;
     if (work_in_tmp) {
-        uint8_t* t = static_cast<uint8_t*>(arena->take(bytes));
         if (perm_in) {
             if ((er = launch_perm(t, src, log_n, batch, false, false, cols, in_rev, st)) != MBLS_SUCCESS) return er;
         } else {
@@ -728,11 +713,9 @@ eIcicleError ntt_call(const mbls_fr_t* input, int size, NTTDir dir, const NTTCon
     }
     if (perm_out && (er = launch_perm(dst, wout, log_n, batch, cols, out_rev, false, false, st)) != MBLS_SUCCESS)
         return er;
-    if (!out_dev) MBLS_TRY(hipMemcpyAsync(output, dst, bytes, hipMemcpyDeviceToHost, st));
     // a staged host input is out of the caller's memory once hipMemcpyAsync returns (pageable)
     // or is the caller's to keep alive (pinned): only a host result forces the wait
-    if (!cfg->is_async || !out_dev) MBLS_TRY(hipStreamSynchronize(st));
-    return MBLS_SUCCESS;
+    return S.close(cfg->is_async);
 }
 
 }  // namespace mbls

@@ -25,17 +25,6 @@ static constexpr int POINT_MAX_BATCH = 1 << 26;  // point_ops.cu:745 MAX_POINT_B
 static constexpr int P2A_RUN = 8;                // points per thread sharing one inversion
 
 template <class F>
-struct PointBytes;
-template <>
-struct PointBytes<Fq> {
-    static constexpr size_t AFF = 96, JAC = 144;
-};
-template <>
-struct PointBytes<Fq2> {
-    static constexpr size_t AFF = 192, JAC = 288;
-};
-
-template <class F>
 __global__ void k_affine_to_jac(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int n) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= n) return;
@@ -96,24 +85,15 @@ eIcicleError convert_call(const void* input, int size, const VecOpsConfig* cfg, 
     // point_ops.cu:767-776: null pointers and sizes outside (0, 2^26] are INVALID_ARGUMENT
     if (!input || !output || !cfg) return MBLS_INVALID_ARGUMENT;
     if (size <= 0 || size > POINT_MAX_BATCH) return MBLS_INVALID_ARGUMENT;
-    constexpr size_t AFF = PointBytes<F>::AFF, JAC = PointBytes<F>::JAC;
-    const size_t in_b = (size_t)size * (TO_AFFINE ? JAC : AFF);
-    const size_t out_b = (size_t)size * (TO_AFFINE ? AFF : JAC);
+    constexpr size_t AFF = PointSize<F>::AFF, JAC = PointSize<F>::JAC;
     hipStream_t st = static_cast<hipStream_t>(cfg->stream);
-    CtxLease lease(st);
-    if (!lease) return lease.error();
-    Arena& A = lease->arena;
-    const bool in_dev = cfg->is_a_on_device, out_dev = cfg->is_result_on_device;
-    eIcicleError er = lease.reserve((in_dev ? 0 : align_up(in_b)) + (out_dev ? 0 : align_up(out_b)));
+    Staging S(st, Staging::LEASE_ALWAYS);
+    const uint8_t* din;
+    uint8_t* dout;
+    S.in(&din, input, (size_t)size * (TO_AFFINE ? JAC : AFF), cfg->is_a_on_device);
+    S.out(&dout, output, (size_t)size * (TO_AFFINE ? AFF : JAC), cfg->is_result_on_device);
+    const eIcicleError er = S.open();
     if (er != MBLS_SUCCESS) return er;
-    const uint8_t* din = static_cast<const uint8_t*>(input);
-    uint8_t* dout = static_cast<uint8_t*>(output);
-    if (!in_dev) {
-        void* t = A.take(in_b);
-        MBLS_TRY(hipMemcpyAsync(t, input, in_b, hipMemcpyHostToDevice, st));
-        din = static_cast<const uint8_t*>(t);
-    }
-    if (!out_dev) dout = static_cast<uint8_t*>(A.take(out_b));
     if (TO_AFFINE) {
         const unsigned threads = (unsigned)((size + P2A_RUN - 1) / P2A_RUN);
         hipLaunchKernelGGL(k_jac_to_affine<F>, dim3((threads + 63) / 64), dim3(64), 0, st, din, dout, size);
@@ -121,9 +101,7 @@ eIcicleError convert_call(const void* input, int size, const VecOpsConfig* cfg, 
         hipLaunchKernelGGL(k_affine_to_jac<F>, dim3((unsigned)((size + 255) / 256)), dim3(256), 0, st, din, dout, size);
     }
     MBLS_TRY(hipGetLastError());
-    if (!out_dev) MBLS_TRY(hipMemcpyAsync(output, dout, out_b, hipMemcpyDeviceToHost, st));
-    if (!cfg->is_async || !out_dev) MBLS_TRY(hipStreamSynchronize(st));
-    return MBLS_SUCCESS;
+    return S.close(cfg->is_async);
 }
 
 }  // namespace mbls

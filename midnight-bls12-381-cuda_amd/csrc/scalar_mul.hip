@@ -213,33 +213,20 @@ static eIcicleError scalar_mul_call(const void* bases, const void* scalars, int 
     // point_ops.cu:1027-1035
     if (!bases || !scalars || !output || !cfg) return MBLS_INVALID_ARGUMENT;
     if (size <= 0 || size > SM_MAX_BATCH) return MBLS_INVALID_ARGUMENT;
-    constexpr size_t AFF = G2 ? 192 : 96, JAC = G2 ? 288 : 144;
-    constexpr size_t ROW = G2 ? SM_G2_ROWS * 288 : SM_G1_ROWS * SM_G1_ROW, CHUNK = G2 ? SM_G2_CHUNK : SM_G1_CHUNK;
-    const size_t n = (size_t)size, b_b = n * AFF, s_b = n * 32, o_b = n * JAC;
-    const size_t t_b = (n < CHUNK ? n : CHUNK) * ROW;
+    using PS = PointSize<typename std::conditional<G2, Fq2, Fq>::type>;
+    constexpr size_t AFF = PS::AFF, JAC = PS::JAC;
+    constexpr size_t ROW = G2 ? SM_G2_ROWS * JAC : SM_G1_ROWS * SM_G1_ROW, CHUNK = G2 ? SM_G2_CHUNK : SM_G1_CHUNK;
+    const size_t n = (size_t)size;
     hipStream_t st = static_cast<hipStream_t>(cfg->stream);
-    CtxLease lease(st);
-    if (!lease) return lease.error();
-    Arena& A = lease->arena;
-    const bool b_dev = cfg->is_a_on_device, s_dev = cfg->is_b_on_device, o_dev = cfg->is_result_on_device;
-    eIcicleError er = lease.reserve(align_up(t_b) + (b_dev ? 0 : align_up(b_b)) + (s_dev ? 0 : align_up(s_b)) +
-                                    (o_dev ? 0 : align_up(o_b)));
+    Staging S(st, Staging::LEASE_ALWAYS);
+    uint8_t *tbl, *dout;
+    const uint8_t *db, *ds;
+    S.scratch(&tbl, (n < CHUNK ? n : CHUNK) * ROW);
+    S.in(&db, bases, n * AFF, cfg->is_a_on_device);
+    S.in(&ds, scalars, n * 32, cfg->is_b_on_device);
+    S.out(&dout, output, n * JAC, cfg->is_result_on_device);
+    const eIcicleError er = S.open();
     if (er != MBLS_SUCCESS) return er;
-    uint8_t* tbl = static_cast<uint8_t*>(A.take(t_b));
-    const uint8_t* db = static_cast<const uint8_t*>(bases);
-    const uint8_t* ds = static_cast<const uint8_t*>(scalars);
-    uint8_t* dout = static_cast<uint8_t*>(output);
-    if (!b_dev) {
-        void* t = A.take(b_b);
-        MBLS_TRY(hipMemcpyAsync(t, bases, b_b, hipMemcpyHostToDevice, st));
-        db = static_cast<const uint8_t*>(t);
-    }
-    if (!s_dev) {
-        void* t = A.take(s_b);
-        MBLS_TRY(hipMemcpyAsync(t, scalars, s_b, hipMemcpyHostToDevice, st));
-        ds = static_cast<const uint8_t*>(t);
-    }
-    if (!o_dev) dout = static_cast<uint8_t*>(A.take(o_b));
     {
         ProfScope prof(G2 ? "scalar_mul.g2" : "scalar_mul.g1", st);
         for (size_t i0 = 0; i0 < n; i0 += CHUNK) {  // stream order serialises the chunks on the table
@@ -261,9 +248,7 @@ static eIcicleError scalar_mul_call(const void* bases, const void* scalars, int 
             MBLS_TRY(hipGetLastError());
         }
     }
-    if (!o_dev) MBLS_TRY(hipMemcpyAsync(output, dout, o_b, hipMemcpyDeviceToHost, st));
-    if (!cfg->is_async || !o_dev) MBLS_TRY(hipStreamSynchronize(st));
-    return MBLS_SUCCESS;
+    return S.close(cfg->is_async);
 }
 
 }  // namespace mbls

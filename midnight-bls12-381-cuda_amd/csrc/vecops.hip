@@ -11,8 +11,6 @@
 // DESIGN.md for the measured rates.
 #include <hip/hip_runtime.h>
 
-#include <optional>
-
 #include <algorithm>
 
 #include "mbls_common.hpp"
@@ -184,59 +182,29 @@ static eIcicleError run_vec_op(const mbls_fr_t* a, const mbls_fr_t* b, size_t si
     if (total == 0) return MBLS_SUCCESS;
     const size_t bytes = total * 32;
 
-    size_t need = 0;
-    if (!scalar_op && !cfg->is_a_on_device) need += align_up(bytes);
-    if (!cfg->is_b_on_device) need += align_up(bytes);
-    if (!cfg->is_result_on_device) need += align_up(bytes);
-    if (scalar_op && !cfg->is_a_on_device) need += align_up(32 * (size_t)batch);
-    // device operands need no scratch: no context lease, hence no `done` event (an event marker
-    // holds the next dispatch ~5 us)
-    std::optional<CtxLease> lease;
-    Arena* arena = nullptr;
-    eIcicleError er = MBLS_SUCCESS;
-    if (need) {
-        lease.emplace(st);
-        if (!*lease) return lease->error();
-        if ((er = lease->reserve(need)) != MBLS_SUCCESS) return er;
-        arena = &(**lease).arena;
-    }
-
-    const uint8_t* da = reinterpret_cast<const uint8_t*>(a);
-    const uint8_t* db = reinterpret_cast<const uint8_t*>(b);
-    uint8_t* dout = reinterpret_cast<uint8_t*>(output);
-    if (!scalar_op && !cfg->is_a_on_device) {
-        void* t = arena->take(bytes);
-        MBLS_TRY(hipMemcpyAsync(t, a, bytes, hipMemcpyHostToDevice, st));
-        da = static_cast<const uint8_t*>(t);
-    }
-    if (!cfg->is_b_on_device) {
-        void* t = arena->take(bytes);
-        MBLS_TRY(hipMemcpyAsync(t, b, bytes, hipMemcpyHostToDevice, st));
-        db = static_cast<const uint8_t*>(t);
-    }
-    if (!cfg->is_result_on_device) dout = static_cast<uint8_t*>(arena->take(bytes));
-
+    // device operands need no scratch: no context lease (Staging::LEASE_IF_STAGED)
+    Staging S(st, Staging::LEASE_IF_STAGED);
+    const uint8_t *da, *db;  // da: the vector a, or the scalar ops' scalars
+    uint8_t* dout;
+    if (!scalar_op) S.in(&da, a, bytes, cfg->is_a_on_device);
+    S.in(&db, b, bytes, cfg->is_b_on_device);
+    S.out(&dout, output, bytes, cfg->is_result_on_device);
+    // scalar ops: one scalar per batch entry (ICICLE v4 batched scalar ops), read on device
+    if (scalar_op) S.in(&da, a, 32 * (size_t)batch, cfg->is_a_on_device);
+    eIcicleError er = S.open();
+    if (er != MBLS_SUCCESS) return er;
     if (scalar_op) {
-        // one scalar per batch entry (ICICLE v4 batched scalar ops), read on device
-        const uint8_t* sv = reinterpret_cast<const uint8_t*>(a);
-        if (!cfg->is_a_on_device) {
-            void* t = arena->take(32 * (size_t)batch);
-            MBLS_TRY(hipMemcpyAsync(t, a, 32 * (size_t)batch, hipMemcpyHostToDevice, st));
-            sv = static_cast<const uint8_t*>(t);
-        }
-        hipLaunchKernelGGL(k_scalar_batch<OP>, dim3(vec_grid(total)), dim3(256), 0, st, dout, sv, db, size,
+        hipLaunchKernelGGL(k_scalar_batch<OP>, dim3(vec_grid(total)), dim3(256), 0, st, dout, da, db, size,
                            (uint32_t)batch, cfg->columns_batch ? 1 : 0, total);
         MBLS_TRY(hipGetLastError());
     } else {
         er = launch<OP>(dout, da, db, Fr{}, total, st);
         if (er != MBLS_SUCCESS) return er;
     }
-    if (!cfg->is_result_on_device) MBLS_TRY(hipMemcpyAsync(output, dout, bytes, hipMemcpyDeviceToHost, st));
     // staged host inputs are copied out of the caller's memory before hipMemcpyAsync returns
     // (pageable) or are the caller's to keep alive (pinned, as in ICICLE): only a host result
     // forces the wait
-    if (!cfg->is_async || !cfg->is_result_on_device) MBLS_TRY(hipStreamSynchronize(st));
-    return MBLS_SUCCESS;
+    return S.close(cfg->is_async);
 }
 
 // sums of `batch` row-major members of `size` elements each -> output[0 .. batch) (device
@@ -245,28 +213,22 @@ static eIcicleError vec_sum(mbls_fr_t* output, const mbls_fr_t* input, size_t si
     if (!output || !input || !cfg) return MBLS_INVALID_POINTER;
     if (batch < 1) batch = 1;
     hipStream_t st = static_cast<hipStream_t>(cfg->stream);
-    CtxLease lease(st);
-    if (!lease) return lease.error();
-    StreamCtx& ctx = *lease;
     const int blocks = size > 0 ? std::min(vec_grid(size), 1024) : 1;
     const size_t in_bytes = 32 * size * (size_t)batch;
-    const bool stage = !cfg->is_a_on_device && in_bytes;
-    eIcicleError er = lease.reserve(align_up(32 * (size_t)blocks) + align_up(32 * (size_t)batch) +
-                                    (stage ? align_up(in_bytes) : 0));
+    Staging S(st, Staging::LEASE_ALWAYS);
+    uint8_t *part, *res;
+    const uint8_t* src;
+    S.scratch(&part, 32 * (size_t)blocks);
+    S.scratch(&res, 32 * (size_t)batch);
+    S.in(&src, input, in_bytes, cfg->is_a_on_device || !in_bytes);  // an empty input is not staged
+    const eIcicleError er = S.open();
     if (er != MBLS_SUCCESS) return er;
-    uint8_t* part = static_cast<uint8_t*>(ctx.arena.take(32 * (size_t)blocks));
-    uint8_t* res = static_cast<uint8_t*>(ctx.arena.take(32 * (size_t)batch));
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(input);
-    if (stage) {
-        void* t = ctx.arena.take(in_bytes);
-        MBLS_TRY(hipMemcpyAsync(t, input, in_bytes, hipMemcpyHostToDevice, st));
-        src = static_cast<const uint8_t*>(t);
-    }
     for (int k = 0; k < batch; ++k) {
         hipLaunchKernelGGL(k_sum_partial, dim3(blocks), dim3(256), 0, st, part, src + 32 * size * (size_t)k, size);
         hipLaunchKernelGGL(k_sum_partial, dim3(1), dim3(256), 0, st, res + 32 * (size_t)k, part, (size_t)blocks);
     }
     MBLS_TRY(hipGetLastError());
+    // the sums are always copied out of `res` (the second pass writes there), D2D too
     MBLS_TRY(hipMemcpyAsync(output, res, 32 * (size_t)batch,
                             cfg->is_result_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
     if (!cfg->is_async || !cfg->is_result_on_device) MBLS_TRY(hipStreamSynchronize(st));

@@ -330,6 +330,24 @@ def test_msm_window_sizes(amd, gh):
         assert gh.decode_icicle("g2", r[0]) == expect2, c
 
 
+def test_msm_g1_unsplit_tiled_sort(amd, gh):
+    """G1 on the unsplit tiled-sort path (keys / vals / ranks + scatter, c > 16 without the GLV
+    split): plain bases reach it only through a narrow bitsize, so otherwise only G2 (c = 17, 18)
+    carves those scratch blocks.  Element-exact against pyref."""
+    plan = amd.msm_plan("g1", 300, bitsize=128, c=18)
+    assert plan["split"] == 1 and plan["c"] == 18
+    g = H.load_golden("msm_g1.json")
+    case = [c for c in g["cases"] if c["name"] == "random_300"][0]
+    _, _, b_mont = _case_arrays(gh, case, "g1")
+    assert len(b_mont) == 300
+    rng = pr.rng(318)
+    sc = [rng.randrange(1 << 128) for _ in range(300)]
+    sc[0], sc[1] = (1 << 128) - 1, 0
+    expect = pr.msm_shared_doubling(sc, [H.pt_from_json(b, "g1") for b in case["bases"]], "g1")
+    r = amd.msm("g1", H.ints_to_limbs(sc, 4), b_mont, bitsize=128, c=18)
+    assert gh.decode_icicle("g1", r[0]) == expect
+
+
 def test_msm_points_standard_form(amd, gh):
     g = H.load_golden("msm_g1.json")
     case = [c for c in g["cases"] if c["name"] == "random_100"][0]
