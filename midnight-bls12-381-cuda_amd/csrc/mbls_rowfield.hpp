@@ -191,16 +191,21 @@ MBLS_DEV RFq add_in(const RFq& a, const RFq& b) {  // a + b < 2^384, no reductio
     return {rowop::add_mask(s, carries_in(G, P))};
 }
 
-// lane-parallel CIOS Montgomery product.  Round i, lane j:  v = a_j b_i + t_j,
-// m = lo(v_0) (-p^-1), w = m p_j + lo(v_j), t_j <- hi(v_j) + hi(w_j) + lo(w_{j+1}).
+// lane-parallel CIOS Montgomery product.  Round i, lane j:  v = a_j b_i + lo(t_j),
+// m = lo(v_0) (-p^-1), w = m p_j + lo(v_j) + hi(t_j) 2^32, t_j <- hi(v_j) + hi(w_j) + lo(w_{j+1}).
+// t_j <= 3 (2^32 - 1), so hi(t_j) <= 2 rides on w's addend and not on v's: a_j b_i + t_j passes
+// 2^64 when a_j = b_i = 0xffffffff and t_j >= 2^33 - 1 (tests/test_gpu_field.py, "ones x ones"),
+// while m p_j + lo(v_j) + 2 2^32 < 2^64 for every limb of p (p_j <= 0xffffaaab).
 // The round's dependent chain is what a lone wave pays for (tools/latbench.hip), so m is taken
 // from t_0 directly:  lo(v_0) (-p^-1) = lo(t_0) (-p^-1) + (a_0 (-p^-1)) b_i  (mod 2^32), one
 // v_mad_u64_u32 on the broadcast lo(t_0) with the addend a_0 (-p^-1) b_i computed off the chain,
-// while v = a b_i + t runs beside it:  bcast -> mad (m) -> mad (w) -> row shift -> add per round
+// while v = a b_i + lo(t) runs beside it:  bcast -> mad (m) -> mad (w) -> row shift -> add per round
 // instead of mad (v) -> bcast -> mul (m) -> mad (w) -> row shift -> add.
-MBLS_DEV uint32_t rf_mad_lo(uint32_t x, uint32_t y, uint32_t z) {  // lo(x*y + z) in ONE instruction
+// lo(x*y + lo(z)) in ONE instruction; z's high word does not reach the low word of the result, so
+// the addend is taken as the register pair it already lives in (no zeroed high half to set up)
+MBLS_DEV uint32_t rf_mad_lo(uint32_t x, uint32_t y, uint64_t z) {
     uint64_t r, c;
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(c) : "v"(x), "s"(y), "v"((uint64_t)z));
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(c) : "v"(x), "s"(y), "v"(z));
     return (uint32_t)r;
 }
 // 64-bit sum of two 32-bit values (opaque to the scheduler: keeps hi(v) + hi(w) off the row shift's
@@ -230,9 +235,9 @@ MBLS_DEV RFq operator*(const RFq& a, const RFq& b) {
 #define MBLS_RF_ROW(I)                                                                    \
     {                                                                                     \
         const uint32_t bi = rowdpp::bcast<I>(b.v);                                        \
-        const uint32_t m = rf_mad_lo(rowdpp::bcast<0>((uint32_t)t), ninv, a0n * bi);      \
-        const uint64_t v = (uint64_t)a.v * bi + t;                                        \
-        const uint64_t w = (uint64_t)m * p + (uint32_t)v;                                 \
+        const uint32_t m = rf_mad_lo(rowdpp::bcast<0>((uint32_t)t), ninv, (uint64_t)a0n * bi); \
+        const uint64_t v = (uint64_t)a.v * bi + (uint32_t)t;                              \
+        const uint64_t w = (uint64_t)m * p + ((t & 0xffffffff00000000ull) | (uint32_t)v); \
         const uint64_t H = rf_add32x2((uint32_t)(v >> 32), (uint32_t)(w >> 32));          \
         t = rf_add64_32(H, rowdpp::from_up((uint32_t)w));                                 \
     }

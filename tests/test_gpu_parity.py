@@ -135,6 +135,111 @@ def test_batch_inv(amd, n):
     assert H.limbs_to_ints(amd.to_numpy_u64(x)) == expect
 
 
+
+# the edge values of tests/golden/gen_golden.py gen_vecops (carry / zero / top-of-range paths)
+VEC_EDGE = [0, 1, 2, pr.FR_R, pr.R - 1, pr.R - 2, (pr.R - 1) // 2, (pr.R + 1) // 2, (1 << 255) % pr.R, (1 << 64) - 1,
+            (1 << 128) - 1, pr.FR_R2]
+# k_vecop: full tiles of VEC_U * 256 = 512 elements, then a partial-tile tail
+VEC_TILE_SIZES = [1, 255, 511, 512, 513, 1025, 3 * 512 + 7]
+
+
+def _edge_pairs(n):
+    """the edge set crossed pairwise and cycled through n elements (the phase moves with n, so the
+    full tiles and the tail see every pair over the sizes)"""
+    k = len(VEC_EDGE)
+    idx = [(i + 5 * n) % (k * k) for i in range(n)]
+    return [VEC_EDGE[j // k] for j in idx], [VEC_EDGE[j % k] for j in idx]
+
+
+_VEC_REF = {"add": lambda x, y: (x + y) % pr.R, "sub": lambda x, y: (x - y) % pr.R, "mul": pr.fr_mont_mul}
+
+
+@pytest.mark.parametrize("n", VEC_TILE_SIZES)
+def test_vecops_edge_values_on_tile_and_tail(amd, n):
+    """add / sub / mul on the pairwise edge set at sizes around the 512-element tile: host and
+    device buffers, and in place (out aliasing a, then b); expected values from pyref"""
+    import torch
+    av, bv = _edge_pairs(n)
+    a, b = H.ints_to_limbs(av, 4), H.ints_to_limbs(bv, 4)
+    for op, fn in _VEC_REF.items():
+        want = [fn(x, y) for x, y in zip(av, bv)]
+        assert H.limbs_to_ints(amd.vec_op(op, a, b)) == want, (op, "host")
+        for alias in (None, "a", "b"):
+            ha, hb = a.copy(), b.copy()
+            da, db = amd.torch_u64(a), amd.torch_u64(b)
+            hout = {None: np.zeros_like(a), "a": ha, "b": hb}[alias]
+            dout = {None: torch.zeros_like(da), "a": da, "b": db}[alias]
+            amd.vec_op(op, ha, hb, out=hout)
+            amd.vec_op(op, da, db, out=dout)
+            torch.cuda.synchronize()
+            assert H.limbs_to_ints(hout) == want, (op, "host, out aliasing", alias)
+            assert H.limbs_to_ints(amd.to_numpy_u64(dout)) == want, (op, "device, out aliasing", alias)
+
+
+@pytest.mark.parametrize("n", VEC_TILE_SIZES)
+def test_scalar_vecops_edge_values_on_tile_and_tail(amd, n):
+    """scalar_mul_vec / scalar_add_vec on the edge set: the ICICLE entry points (host, device, in
+    place) and the device-pointer entry points, which run k_vecop's tile and tail paths"""
+    import ctypes
+    import torch
+    _, bv = _edge_pairs(n)
+    b = H.ints_to_limbs(bv, 4)
+    L = amd.lib()
+    cfg = amd.vec_config(is_a_on_device=True, is_b_on_device=True, is_result_on_device=True)
+    for sv in (pr.R - 1, VEC_EDGE[n % len(VEC_EDGE)], pr.rng(n).randrange(pr.R)):
+        s = np.ascontiguousarray(H.ints_to_limbs([sv], 4)[0])
+        for op, raw, fn in (("scalar_mul", "scalar_mul_vec_cuda", pr.fr_mont_mul), ("scalar_add", "scalar_add_vec_cuda",
+                                                                                   lambda x, y: (x + y) % pr.R)):
+            want = [fn(sv, y) for y in bv]
+            assert H.limbs_to_ints(amd.vec_op(op, s, b)) == want, (op, "host")
+            hb = b.copy()
+            amd.vec_op(op, s, hb, out=hb)
+            assert H.limbs_to_ints(hb) == want, (op, "host, in place")
+            for inplace in (False, True):
+                db = amd.torch_u64(b)
+                out = db if inplace else torch.zeros_like(db)
+                amd.vec_op(op, amd.torch_u64(s.reshape(1, 4)), db, out=out)
+                torch.cuda.synchronize()
+                assert H.limbs_to_ints(amd.to_numpy_u64(out)) == want, (op, "device, in place" if inplace else "device")
+                db = amd.torch_u64(b)
+                out = db if inplace else torch.zeros_like(db)
+                amd.check(getattr(L, raw)(amd._p(out), amd._p(s), amd._p(db), n, ctypes.byref(cfg)), raw)
+                torch.cuda.synchronize()
+                assert H.limbs_to_ints(amd.to_numpy_u64(out)) == want, (raw, "in place" if inplace else "out of place")
+
+
+def _edge_vectors(n):
+    """named vectors of n elements on the edge set: cycled, all r - 1, alternating x, r - x"""
+    x = (1 << 255) % pr.R
+    return {"edge": [VEC_EDGE[(i + n) % len(VEC_EDGE)] for i in range(n)], "all r-1": [pr.R - 1] * n,
+            "x, r-x": [x if i % 2 == 0 else pr.R - x for i in range(n)]}
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 512, 1025])
+def test_vec_sum_edge_values(amd, n):
+    for name, vals in _edge_vectors(n).items():
+        out = amd.vec_sum(amd.torch_u64(H.ints_to_limbs(vals, 4)))
+        assert H.limbs_to_ints(out)[0] == sum(vals) % pr.R, name
+    assert sum(_edge_vectors(512)["x, r-x"]) % pr.R == 0  # the alternating vector sums to zero
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 513])
+def test_batch_inv_edge_values(amd, n):
+    """the edge set as Montgomery-form inputs (v = x R -> x^-1 R = v^-1 R^2; 0 -> 0), in place too"""
+    import torch
+    r2 = pr.FR_R2
+    for name, vals in _edge_vectors(n).items():
+        expect = [pow(v, -1, pr.R) * r2 % pr.R if v else 0 for v in vals]
+        x = amd.torch_u64(H.ints_to_limbs(vals, 4))
+        out = torch.zeros_like(x)
+        amd.batch_inv(x, out)
+        torch.cuda.synchronize()
+        assert H.limbs_to_ints(amd.to_numpy_u64(out)) == expect, name
+        amd.batch_inv(x, x)
+        torch.cuda.synchronize()
+        assert H.limbs_to_ints(amd.to_numpy_u64(x)) == expect, (name, "in place")
+
+
 # ----------------------------------------------------------------------------- NTT
 @pytest.mark.parametrize("ordering", ["NN", "NR", "RN", "RR", "NM", "MN"])
 def test_ntt_orderings(amd, ordering):
