@@ -163,7 +163,12 @@ eIcicleError bls12_381_icicle_g2_msm_precompute_bases(const mbls_g2_affine_t* in
 /* NTT (reference ntt_kernels.cu:1907-1943, icicle_field_api.cu:363-383)                  */
 /* Semantics follow the CPU path (core/ntt.rs:1488-1603, best_fft): forward
  * out_j = sum_i in_i w^(ij), inverse = n^-1 sum_j in_j w^(-ij), w = ROOT_OF_UNITY^(2^(32-k))
- * for size 2^k, natural order in and out (kNN).                                          */
+ * for size 2^k, natural order in and out (kNN).
+ * Input contract: every input element is canonical (< r, Montgomery form).  The transform keeps
+ * lazy values in [0, 2r) and its first butterflies add the raw inputs, so a larger value breaks
+ * that invariant and the result is unspecified; outputs are always canonical.  A coset generator
+ * (NTTConfig.coset_gen, or the argument of bls12_381_coset_ntt_cuda) that is zero mod r -- a
+ * zero-initialised NTTConfig -- is rejected with INVALID_ARGUMENT; Montgomery one means no coset. */
 /* ------------------------------------------------------------------------------------ */
 eIcicleError bls12_381_ntt_init_domain_cuda(const mbls_fr_t* root_of_unity, const NTTInitDomainConfig* config);
 eIcicleError bls12_381_ntt_release_domain_cuda(void);

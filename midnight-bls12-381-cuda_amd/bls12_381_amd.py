@@ -334,18 +334,29 @@ ORDERINGS = {"NN": 0, "NR": 1, "RN": 2, "RR": 3, "NM": 4, "MN": 5}
 
 
 def ntt(x, inverse=False, out=None, batch=1, stream=None, is_async=False, coset_gen=None, ordering="NN",
-        columns_batch=False):
-    """x: (batch*n, 4) uint64 numpy (host) or torch (device)."""
+        columns_batch=False, entry="ntt"):
+    """x: (batch*n, 4) uint64 numpy (host) or torch (device).  entry: the exported symbol that takes
+    the call -- "ntt" (bls12_381_ntt_cuda), "field" (bls12_381_field_ntt_cuda), both with the coset
+    generator in the config, or "coset" (bls12_381_coset_ntt_cuda: the generator as an argument,
+    the config's left at its default)."""
     total = x.shape[0]
     n = total // batch
     if out is None:
         out = np.zeros((total, 4), dtype=np.uint64) if isinstance(x, np.ndarray) else None
     kw = dict(batch_size=batch, are_inputs_on_device=_is_dev(x), are_outputs_on_device=_is_dev(out),
               is_async=is_async, stream=stream, ordering=ORDERINGS[ordering], columns_batch=columns_batch)
-    if coset_gen is not None:
+    if coset_gen is not None and entry != "coset":
         kw["coset_gen"] = coset_gen
     cfg = ntt_config(**kw)
-    check(lib().bls12_381_ntt_cuda(_p(x), n, 1 if inverse else 0, ctypes.byref(cfg), _p(out)), "ntt")
+    d = 1 if inverse else 0
+    if entry == "coset":
+        g = FrC()
+        for i in range(4):
+            g.limbs[i] = int(cfg.coset_gen.limbs[i] if coset_gen is None else coset_gen[i])
+        check(lib().bls12_381_coset_ntt_cuda(_p(x), n, d, ctypes.byref(g), ctypes.byref(cfg), _p(out)), "coset_ntt")
+    else:
+        fn = {"ntt": lib().bls12_381_ntt_cuda, "field": lib().bls12_381_field_ntt_cuda}[entry]
+        check(fn(_p(x), n, d, ctypes.byref(cfg), _p(out)), entry)
     return out
 
 

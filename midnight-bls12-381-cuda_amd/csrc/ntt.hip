@@ -17,9 +17,10 @@
 // (A single w_(2^K)^i table read at stride 2^(K-s) put every lane on its own cache line:
 // measured 3.5x the data bytes fetched by the later passes, profiles/r01.)
 //
-// Kernel structure: ceil(k / 10) passes, each a LDS-resident tile of T = 1024 elements
-// (32 KiB) doing up to 10 radix-2 DIT stages between __syncthreads.  Pass 1 fuses the
-// bit-reversal permutation into its gather: it reads C adjacent columns of the input viewed
+// Kernel structure: ceil(k / MBLS_NTT_PASS_STAGES) = ceil(k / 8) passes of near-equal stage
+// counts, each a LDS-resident tile of T = 2^MBLS_NTT_TILE_LOG = 1024 elements (32 KiB) doing up
+// to 8 radix-2 DIT stages (2^L rows x 2^(10 - L) adjacent columns) between __syncthreads.
+// Pass 1 fuses the bit-reversal permutation into its gather: it reads C adjacent columns of the input viewed
 // as a 2^L x 2^(k-L) matrix (coalesced C*32-byte rows) and writes contiguous DIT blocks.
 // Later passes read/write tiles of 2^L strided rows x C adjacent columns in place.  The
 // inverse's n^-1 scaling is fused into the last pass's store.
@@ -636,6 +637,18 @@ eIcicleError ntt_call(const mbls_fr_t* input, int size, NTTDir dir, const NTTCon
     if (log_n < 0) return MBLS_INVALID_ARGUMENT;
     const int ord = (int)cfg->ordering;
     if (ord < MBLS_ORDERING_NN || ord > MBLS_ORDERING_MN) return MBLS_INVALID_ARGUMENT;
+    // coset: forward evaluates on g*H (pre-scale by g^i); inverse post-scales by g^-i.  A generator
+    // that is zero mod r (a zero-initialised NTTConfig) has no inverse and spans no coset
+    bool coset = false;
+    uint64_t g[4];
+    if (coset_gen) {
+        memcpy(g, coset_gen->limbs, 32);
+        uint64_t gr[4];
+        hfr_mul(gr, g, HFR_R2);  // g R mod r, canonical for any 256-bit g
+        const uint64_t zero[4] = {0, 0, 0, 0};
+        if (hfr_eq(gr, zero)) return MBLS_INVALID_ARGUMENT;
+        coset = !hfr_eq(g, HFR_ONE);
+    }
     const bool in_rev = ord == MBLS_ORDERING_RN || ord == MBLS_ORDERING_RR || ord == MBLS_ORDERING_MN;
     const bool out_rev = ord == MBLS_ORDERING_NR || ord == MBLS_ORDERING_RR || ord == MBLS_ORDERING_NM;
     const bool cols = cfg->columns_batch;
@@ -660,13 +673,6 @@ eIcicleError ntt_call(const mbls_fr_t* input, int size, NTTDir dir, const NTTCon
     const size_t bytes = (size_t)size * 32 * (size_t)batch;
     const size_t total = (size_t)size * batch;
     const bool inverse = (dir == MBLS_NTT_INVERSE);
-    // coset: forward evaluates on g*H (pre-scale by g^i); inverse post-scales by g^-i
-    bool coset = false;
-    uint64_t g[4];
-    if (coset_gen) {
-        memcpy(g, coset_gen->limbs, 32);
-        coset = !hfr_eq(g, HFR_ONE);
-    }
     const bool perm_in = (in_rev || cols) && log_n > 0;
     const bool perm_out = (out_rev || cols) && log_n > 0;
     const bool in_dev = cfg->are_inputs_on_device, out_dev = cfg->are_outputs_on_device;

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+import ntt_model
 from helpers import pyref as pr
 
 pytestmark = pytest.mark.gpu
@@ -295,7 +296,7 @@ def test_ntt_golden(amd):
         assert H.limbs_to_ints(inv) == [H.hx(v) for v in case["inverse"]], case["name"]
 
 
-@pytest.mark.parametrize("log_n", [11, 12, 15, 17, 20])
+@pytest.mark.parametrize("log_n", ntt_model.ORACLE_CHECKED_LOG_N["test_gpu_parity::test_ntt_vs_oracle"])
 def test_ntt_vs_oracle(amd, log_n):
     import torch
     amd.ntt_init_domain()
@@ -313,7 +314,7 @@ def test_ntt_vs_oracle(amd, log_n):
     assert np.array_equal(amd.to_numpy_u64(z), xn)  # exact round trip
 
 
-@pytest.mark.parametrize("log_n", [23, 24])
+@pytest.mark.parametrize("log_n", ntt_model.ORACLE_CHECKED_LOG_N["test_gpu_parity::test_ntt_past_init_tables_vs_oracle"])
 def test_ntt_past_init_tables_vs_oracle(amd, log_n):
     """sizes above the 2^22 stage tables built at init_domain: the tables are extended on first
     use (ntt.hip build_domain); forward against the oracle's best_fft DFT, exact round trip, and
