@@ -265,6 +265,34 @@ eIcicleError mbls_g2_scalar_mul(const mbls_g2_affine_t* bases, const mbls_fr_t* 
                                 bool scalars_montgomery, const VecOpsConfig* config, mbls_g2_projective_t* output);
 
 /* ------------------------------------------------------------------------------------ */
+/* G1 EC-NTT: the NTT over G1 points (no reference counterpart: the reference derives the Lagrange
+ * SRS on the CPU, g_to_lagrange).  For size = 2^k and w = ROOT_OF_UNITY^(2^(32-k)), the root of the
+ * Fr NTT of that size (bls12_381_ntt_get_rou_from_domain(k)):
+ *   forward  out_j = sum_i [w^(ij)] P_i
+ *   inverse  out_i = [n^-1] sum_j [w^(-ij)] P_j
+ * natural order in and out.  The inverse of a monomial SRS P_j = [s^j] G is the Lagrange SRS
+ * [L_i(s)] G.
+ *   points: Montgomery affine, 96 bytes, identity = all zero, in and out.  The output is canonical
+ *     affine: a result has exactly one byte representation.  Inputs are ASSUMED to lie in the
+ *     order-r subgroup, as for scalar_mul and the MSM: the GLV split relies on phi = [lambda],
+ *     which holds only there (not checked).
+ *   config: stream, are_inputs_on_device, are_outputs_on_device and is_async are honoured.  Host
+ *     buffers are staged through the leased scratch context, which also holds the work arrays; a
+ *     host output is synchronous, a device output synchronises unless is_async.  input == output
+ *     (the same device pointer) is allowed; a partial overlap is undefined.
+ *   errors, before any device work: a null input, output or config gives INVALID_POINTER (the
+ *     NTT's convention); INVALID_ARGUMENT for size < 1, not a power of two or > 2^26, for log2 size
+ *     above the order of the initialised NTT domain (32 with none initialised), for batch_size
+ *     other than 0 or 1, for columns_batch, for an ordering other than NN and for a coset_gen other
+ *     than Montgomery one (a zero-initialised config included, as for the NTT).  The call reads the
+ *     domain's order only: it neither needs nor builds the Fr twiddle tables.
+ *   timing: NOT constant time -- table lookups and branches depend on the scalars' digits.  Here
+ *     the scalars are public roots of unity, so nothing secret is exposed.                     */
+/* ------------------------------------------------------------------------------------ */
+eIcicleError mbls_g1_ecntt(const mbls_g1_affine_t* input, int size, NTTDir dir, const NTTConfig* config,
+                           mbls_g1_affine_t* output);
+
+/* ------------------------------------------------------------------------------------ */
 /* library utilities (no reference counterpart; used by the host API, tests and bench)   */
 /* ------------------------------------------------------------------------------------ */
 const char* mbls_version(void);

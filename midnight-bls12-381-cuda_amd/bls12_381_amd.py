@@ -79,7 +79,7 @@ EXPORTED = [
     "bls12_381_g1_affine_to_projective", "bls12_381_g1_projective_to_affine", "bls12_381_g2_projective_to_affine",
     "mbls_msm_plan", "mbls_msm_accumulate_event", "mbls_msm_accumulate_event_drop", "mbls_msm_precompute_strict",
     "bls12_381_g1_scalar_mul", "bls12_381_g1_scalar_mul_glv", "bls12_381_g2_scalar_mul",
-    "mbls_g1_scalar_mul", "mbls_g2_scalar_mul",
+    "mbls_g1_scalar_mul", "mbls_g2_scalar_mul", "mbls_g1_ecntt",
 ]
 
 _LIB = None
@@ -128,6 +128,7 @@ def lib():
         "bls12_381_g1_scalar_mul": [P, P, i32, P, P], "bls12_381_g1_scalar_mul_glv": [P, P, i32, P, P],
         "bls12_381_g2_scalar_mul": [P, P, i32, P, P],
         "mbls_g1_scalar_mul": [P, P, i32, b, P, P], "mbls_g2_scalar_mul": [P, P, i32, b, P, P],
+        "mbls_g1_ecntt": [P, i32, i32, P, P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -357,6 +358,22 @@ def ntt(x, inverse=False, out=None, batch=1, stream=None, is_async=False, coset_
     else:
         fn = {"ntt": lib().bls12_381_ntt_cuda, "field": lib().bls12_381_field_ntt_cuda}[entry]
         check(fn(_p(x), n, d, ctypes.byref(cfg), _p(out)), entry)
+    return out
+
+
+def ecntt(points, inverse=False, out=None, stream=None, is_async=False):
+    """G1 EC-NTT (mbls_g1_ecntt): `points` (n, 12) uint64 Montgomery affine, n a power of two, numpy
+    (host) or torch (device).  forward out_j = sum_i [w^(ij)] P_i, inverse out_i = [n^-1] sum_j
+    [w^(-ij)] P_j with the Fr NTT's root w of that size, natural order: the inverse of a monomial
+    SRS [s^j] G is the Lagrange SRS.  Returns (n, 12) canonical Montgomery affine, host numpy unless
+    `out` is a device tensor (`out` may be `points`).  Points are assumed to lie in the order-r
+    subgroup."""
+    n = points.shape[0]
+    if out is None:
+        out = np.zeros((n, 12), dtype=np.uint64)
+    cfg = ntt_config(are_inputs_on_device=_is_dev(points), are_outputs_on_device=_is_dev(out), is_async=is_async,
+                     stream=stream)
+    check(lib().mbls_g1_ecntt(_p(points), n, 1 if inverse else 0, ctypes.byref(cfg), _p(out)), "mbls_g1_ecntt")
     return out
 
 

@@ -187,6 +187,15 @@ struct AccEventGuard {
     }
 };
 
+// What ecntt.hip takes from its neighbours.
+// ntt.hip: the current device's domain bounds sizes at 2^order_log (32 with no domain initialised):
+// INVALID_ARGUMENT past it, else w = the canonical root of order 2^log_n (its inverse if `inverse`)
+// and n_inv = 2^-log_n, both Montgomery.  No stage table is built or extended.
+eIcicleError ntt_domain_roots(int log_n, bool inverse, uint64_t* w, uint64_t* n_inv);
+bool fr_is_montgomery_one(const uint64_t* a);
+// points.hip: enqueue k_jac_to_affine<Fq> over n G1 Jacobian points (device pointers, no overlap)
+eIcicleError g1_jac_to_affine_device(const uint8_t* in, uint8_t* out, int n, hipStream_t st);
+
 // Stage profiler: when enabled (mbls_profile_enable / MBLS_PROFILE=1) a ProfScope records a
 // hipEvent pair on the stream around the enclosed launches; mbls_profile_read() sums the
 // elapsed times per stage name.  Disabled: one branch, no events.

@@ -724,6 +724,24 @@ eIcicleError ntt_call(const mbls_fr_t* input, int size, NTTDir dir, const NTTCon
     return S.close(cfg->is_async);
 }
 
+// The EC-NTT's view of the domain (mbls_common.hpp; ecntt.hip): the order bound and the canonical
+// roots only -- it neither builds nor extends the stage tables.
+eIcicleError ntt_domain_roots(int log_n, bool inverse, uint64_t* w, uint64_t* n_inv) {
+    {
+        std::lock_guard<std::mutex> lk(g_domain_mu);
+        Domain* dom = current_domain();
+        if (!dom) return MBLS_INVALID_DEVICE;
+        if (log_n > dom->order_log) return MBLS_INVALID_ARGUMENT;  // beyond the initialised root
+    }
+    canonical_omega(w, log_n);
+    if (inverse) hfr_inv(w, w);
+    uint64_t nm[4] = {(uint64_t)1 << log_n, 0, 0, 0};
+    hfr_mul(nm, nm, HFR_R2);  // n in Montgomery form
+    hfr_inv(n_inv, nm);
+    return MBLS_SUCCESS;
+}
+bool fr_is_montgomery_one(const uint64_t* a) { return hfr_eq(a, HFR_ONE); }
+
 }  // namespace mbls
 
 using namespace mbls;

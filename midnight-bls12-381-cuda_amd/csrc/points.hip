@@ -104,6 +104,15 @@ eIcicleError convert_call(const void* input, int size, const VecOpsConfig* cfg, 
     return S.close(cfg->is_async);
 }
 
+// k_jac_to_affine<Fq> over device buffers for the other translation units (mbls_common.hpp; the
+// EC-NTT normalises its Jacobian butterflies with it after every stage)
+eIcicleError g1_jac_to_affine_device(const uint8_t* in, uint8_t* out, int n, hipStream_t st) {
+    const unsigned threads = (unsigned)((n + P2A_RUN - 1) / P2A_RUN);
+    hipLaunchKernelGGL(k_jac_to_affine<Fq>, dim3((threads + 63) / 64), dim3(64), 0, st, in, out, n);
+    MBLS_TRY(hipGetLastError());
+    return MBLS_SUCCESS;
+}
+
 }  // namespace mbls
 
 using namespace mbls;
