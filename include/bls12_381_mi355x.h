@@ -125,6 +125,9 @@ VecOpsConfig mbls_default_vec_ops_config(void);
 /* ------------------------------------------------------------------------------------ */
 /* MSM                                                                                    */
 /* ------------------------------------------------------------------------------------ */
+/* Every MSM entry below splits its scalars with the endomorphisms (G1: phi = [lambda], G2:
+ * psi = [z]); both identities hold only on the order-r subgroup, so the bases are ASSUMED to lie
+ * in it (not checked here; see mbls_g*_check_points).                                       */
 /* Raw kernel-level MSM, reference icicle_curve_api.cu:679-705 (bls12_381_g1_msm_cuda /
  * bls12_381_g2_msm_cuda -> msm::msm_cuda, msm_kernels.cu:603-903):
  *   scalars STANDARD form, bases Montgomery affine, result = Jacobian Montgomery point
@@ -241,7 +244,8 @@ eIcicleError bls12_381_g2_projective_to_affine(const mbls_g2_projective_t* input
  *     entry applies).  The mbls_* forms read Montgomery scalars when scalars_montgomery is set.
  *   bases: Montgomery affine; the identity is the all-zero point and gives the identity for every
  *     scalar.  Bases are ASSUMED to lie in the order-r subgroup, as for the MSM: the GLV / psi
- *     splits rely on phi = [lambda] and psi = [z], which hold only there (not checked).
+ *     splits rely on phi = [lambda] and psi = [z], which hold only there (not checked here; see
+ *     mbls_g*_check_points).
  *   output: Jacobian Montgomery (X, Y, Z), x = X/Z^2, y = Y/Z^3, identity Z = 0 -- the form
  *     bls12_381_g*_projective_to_affine takes.  Input and output must not overlap.
  *   placement: config->is_a_on_device the bases, is_b_on_device the scalars, is_result_on_device
@@ -275,7 +279,7 @@ eIcicleError mbls_g2_scalar_mul(const mbls_g2_affine_t* bases, const mbls_fr_t* 
  *   points: Montgomery affine, 96 bytes, identity = all zero, in and out.  The output is canonical
  *     affine: a result has exactly one byte representation.  Inputs are ASSUMED to lie in the
  *     order-r subgroup, as for scalar_mul and the MSM: the GLV split relies on phi = [lambda],
- *     which holds only there (not checked).
+ *     which holds only there (not checked here; see mbls_g*_check_points).
  *   config: stream, are_inputs_on_device, are_outputs_on_device and is_async are honoured.  Host
  *     buffers are staged through the leased scratch context, which also holds the work arrays; a
  *     host output is synchronous, a device output synchronises unless is_async.  input == output
@@ -291,6 +295,44 @@ eIcicleError mbls_g2_scalar_mul(const mbls_g2_affine_t* bases, const mbls_fr_t* 
 /* ------------------------------------------------------------------------------------ */
 eIcicleError mbls_g1_ecntt(const mbls_g1_affine_t* input, int size, NTTDir dir, const NTTConfig* config,
                            mbls_g1_affine_t* output);
+
+/* ------------------------------------------------------------------------------------ */
+/* batch point validation: is every point canonical, on the curve and in the order-r subgroup?
+ * (No reference counterpart: the reference has g1_is_on_curve, point.cuh:339, as a device helper
+ * only and no subgroup test.)  The MSM, scalar_mul and EC-NTT entries assume subgroup members
+ * because their GLV / psi splits are wrong elsewhere; this is the call that establishes it, once,
+ * when an SRS is uploaded.  status[i] is the FIRST failing test of point i in the order of the
+ * enum; 0 and 1 are valid, >= 2 invalid.
+ *   membership: the endomorphism criteria of M. Scott, "A note on group membership tests for G1,
+ *     G2 and GT on BLS pairing-friendly curves" -- G1: [z^2] P - P == phi(P), a 128-bit chain;
+ *     G2: psi(P) == [z] P, a 64-bit chain -- exact on curve points for the library's beta / psi.
+ *   points: affine, Montgomery when points_montgomery, else standard form (as the MSM's
+ *     are_points_montgomery_form = false).  The canonical test reads the raw words either way, the
+ *     conversion follows it.  The identity is only the all-zero encoding: (0, p) is NONCANONICAL.
+ *   outputs: status, `size` bytes, placed by config->is_result_on_device; n_invalid, a HOST
+ *     pointer, receives the number of points with status >= 2.  Either may be NULL, not both.
+ *   placement: config->is_a_on_device the points.  Host buffers are staged through the leased
+ *     scratch context; a host output (a host status, or a non-NULL n_invalid) makes the call
+ *     synchronous, otherwise it synchronises unless is_async.  batch_size and columns_batch are
+ *     not read.
+ *   errors: a null points or config, both outputs null, size <= 0 or size > 2^26 give
+ *     INVALID_ARGUMENT before any device work (scalar_mul's convention).  Invalid points are data,
+ *     not an error: the call returns SUCCESS.
+ *   timing: NOT constant time -- a lane leaves at its first failing test.  Points to validate are
+ *     public, so nothing secret is involved.                                                   */
+/* ------------------------------------------------------------------------------------ */
+typedef enum {
+    MBLS_POINT_OK = 0,            /* canonical, on the curve, in the order-r subgroup          */
+    MBLS_POINT_IDENTITY = 1,      /* the all-zero identity encoding: a member, reported apart  */
+    MBLS_POINT_NONCANONICAL = 2,  /* some coordinate (G2: some component) is >= p             */
+    MBLS_POINT_OFF_CURVE = 3,     /* canonical, but y^2 != x^3 + b                             */
+    MBLS_POINT_OFF_SUBGROUP = 4   /* on the curve, but [r]P != O                               */
+} mbls_point_status;
+
+eIcicleError mbls_g1_check_points(const mbls_g1_affine_t* points, int size, bool points_montgomery,
+                                  const VecOpsConfig* config, uint8_t* status, uint64_t* n_invalid);
+eIcicleError mbls_g2_check_points(const mbls_g2_affine_t* points, int size, bool points_montgomery,
+                                  const VecOpsConfig* config, uint8_t* status, uint64_t* n_invalid);
 
 /* ------------------------------------------------------------------------------------ */
 /* library utilities (no reference counterpart; used by the host API, tests and bench)   */

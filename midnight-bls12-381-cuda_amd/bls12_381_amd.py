@@ -80,6 +80,7 @@ EXPORTED = [
     "mbls_msm_plan", "mbls_msm_accumulate_event", "mbls_msm_accumulate_event_drop", "mbls_msm_precompute_strict",
     "bls12_381_g1_scalar_mul", "bls12_381_g1_scalar_mul_glv", "bls12_381_g2_scalar_mul",
     "mbls_g1_scalar_mul", "mbls_g2_scalar_mul", "mbls_g1_ecntt",
+    "mbls_g1_check_points", "mbls_g2_check_points",
 ]
 
 _LIB = None
@@ -129,6 +130,7 @@ def lib():
         "bls12_381_g2_scalar_mul": [P, P, i32, P, P],
         "mbls_g1_scalar_mul": [P, P, i32, b, P, P], "mbls_g2_scalar_mul": [P, P, i32, b, P, P],
         "mbls_g1_ecntt": [P, i32, i32, P, P],
+        "mbls_g1_check_points": [P, i32, b, P, P, P], "mbls_g2_check_points": [P, i32, b, P, P, P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -282,7 +284,8 @@ def scalar_mul(group, bases, scalars, *, scalars_mont=False, out=None, stream=No
     (n, 12 | 24) uint64 Montgomery affine, `scalars` (n, 4) uint64, standard form unless
     scalars_mont; each numpy (host) or torch (device).  Returns (n, 18 | 36) Jacobian Montgomery
     (identity Z = 0), host numpy unless `out` is a device tensor; convert_points(group,
-    "to_affine", ...) gives affine points.  Bases are assumed to lie in the order-r subgroup."""
+    "to_affine", ...) gives affine points.  Bases are assumed to lie in the order-r subgroup
+    (check_points establishes it)."""
     n = bases.shape[0]
     assert scalars.shape[0] == n
     if out is None:
@@ -292,6 +295,29 @@ def scalar_mul(group, bases, scalars, *, scalars_mont=False, out=None, stream=No
     name = "mbls_g1_scalar_mul" if group == "g1" else "mbls_g2_scalar_mul"
     check(getattr(lib(), name)(_p(bases), _p(scalars), n, bool(scalars_mont), ctypes.byref(cfg), _p(out)), name)
     return out
+
+
+# mbls_point_status (include/bls12_381_mi355x.h): 0 and 1 are valid, >= 2 invalid
+POINT_OK, POINT_IDENTITY, POINT_NONCANONICAL, POINT_OFF_CURVE, POINT_OFF_SUBGROUP = range(5)
+
+
+def check_points(group, pts, *, points_mont=True, out=None, count=True, stream=None, is_async=False):
+    """Batch point validation (mbls_g*_check_points): `pts` (n, 12 | 24) uint64 affine, Montgomery
+    unless points_mont is False, numpy (host) or torch (device).  Returns (status, n_invalid):
+    status[i] is the first failing test of point i (POINT_*), a host uint8 array, or `out` when it
+    is a device uint8 tensor, or None for out=False (count only); n_invalid is the number of
+    statuses >= 2, or None for count=False (then a device `out` with is_async does not wait)."""
+    n = pts.shape[0]
+    if out is None:
+        out = np.zeros(n, dtype=np.uint8)
+    elif out is False:
+        out = None
+    cnt = ctypes.c_uint64(0) if count else None
+    cfg = vec_config(is_a_on_device=_is_dev(pts), is_result_on_device=_is_dev(out), stream=stream, is_async=is_async)
+    name = "mbls_g1_check_points" if group == "g1" else "mbls_g2_check_points"
+    check(getattr(lib(), name)(_p(pts), n, bool(points_mont), ctypes.byref(cfg), _p(out),
+                               ctypes.byref(cnt) if count else None), name)
+    return out, (int(cnt.value) if count else None)
 
 
 def vec_sum(x, out=None, stream=None):

@@ -240,6 +240,23 @@ static __constant__ uint32_t PSI_CY1_MONT[12] = {0x5aa30fdau, 0x7bcfa7a2u, 0x2a9
                                                  0x6b4ebef1u, 0x2f088dd8u, 0xda74d4a7u, 0xd1ca2087u,
                                                  0x96cebc1du, 0x2da25966u, 0xbbfd87d2u, 0x0e2b7eedu};
 
+// psi(P) alone, of a pair-sliced point (mbls_pairfield.hpp: lane 2k holds c0, lane 2k+1 c1): the
+// field values psi_images gives q1, Montgomery; identity (0, 0) maps to itself.  The subgroup test
+// of check_points.hip compares it with [z] P.
+MBLS_DEV Affine<PFq2> psi_image(const Affine<PFq2>& p) {
+    const bool j = pairdpp::odd();
+    Fq cx1, cy;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        cx1.v[k] = PSI_CX1_MONT[k];
+        cy.v[k] = j ? PSI_CY1_MONT[k] : PSI_CY0_MONT[k];
+    }
+    Affine<PFq2> q;
+    q.x = PFq2{partner(p.x.v) * cx1};                                // x1 CX1 + x0 CX1 u
+    q.y = PFq2{select(j, neg(p.y.v), p.y.v)} * PFq2{cy};             // conj(y) * CY
+    return q;
+}
+
 // psi(P), psi^2(P), psi^3(P) of one G2 point, Montgomery
 MBLS_DEV void psi_images(const Affine<Fq2>& p, Affine<Fq2>& q1, Affine<Fq2>& q2, Affine<Fq2>& q3) {
     Fq cx1;
