@@ -335,6 +335,59 @@ eIcicleError mbls_g2_check_points(const mbls_g2_affine_t* points, int size, bool
                                   const VecOpsConfig* config, uint8_t* status, uint64_t* n_invalid);
 
 /* ------------------------------------------------------------------------------------ */
+/* batch point compression and decompression, in the ZCash encoding that ceremony transcripts, SRS
+ * files and the blst-backed crates' to_compressed / from_compressed use.  (No reference
+ * counterpart: the reference has no serialization and no square root.)
+ *   format: a G1 record is 48 bytes, x as a big-endian integer; a G2 record is 96 bytes, x.c1 in
+ *     bytes 0..47 then x.c0 in bytes 48..95.  The top three bits of byte 0 are flags: C (bit 7),
+ *     the compressed form, always 1; I (bit 6), infinity, with every other bit of the record zero
+ *     (c0 00 .. 00); S (bit 5), y is the larger of {y, p - y} as standard-form integers,
+ *     y > (p - 1) / 2 -- for G2 comparing y.c1 first and y.c0 only when y.c1 == 0.
+ *   decompress: status[i] is the FIRST failing test of record i in the order BAD_FLAGS, IDENTITY,
+ *     NONCANONICAL, NO_POINT; 0 and 1 are valid, >= 2 invalid, and 0..3 line up with
+ *     mbls_point_status, so the maximum of this status and a later check_points status is
+ *     meaningful.  Status 0 writes the canonical (x, y) with the root chosen by S, Montgomery when
+ *     points_montgomery, else standard form; every other status writes the all-zero point, so the
+ *     output is deterministic and the status tells a rejected record from a real identity.
+ *     y = sqrt(x^3 + b) by one fixed exponent chain (p == 3 mod 4), in G2 through the norm; a point
+ *     that is written satisfies the curve equation by construction.  NO SUBGROUP TEST is made:
+ *     for untrusted input mbls_g*_check_points on the output is the next step.
+ *   compress: the inverse.  Inputs are assumed to be canonical curve points or the all-zero
+ *     identity, which gives the infinity encoding; NOTHING IS VALIDATED (a point off the curve or
+ *     a non-canonical coordinate gives a record that does not decode to it).
+ *   outputs of decompress: points, `size` affine points; status, `size` bytes; both placed by
+ *     config->is_result_on_device; n_invalid, a HOST pointer, receives the number of records with
+ *     status >= 2.  status and n_invalid may each be NULL, also both.
+ *   placement: config->is_a_on_device the input (bytes for decompress, points for compress),
+ *     config->is_result_on_device the output.  Host buffers are staged through the leased scratch
+ *     context; a host output (or a non-NULL n_invalid) makes the call synchronous, otherwise it
+ *     synchronises unless is_async.  batch_size and columns_batch are not read.
+ *   errors: INVALID_ARGUMENT before any device work (scalar_mul's convention) for a null bytes,
+ *     points or config, for size <= 0 or size > 2^26, and for a DEVICE byte or point buffer that is
+ *     not 16-byte aligned (records move as 16-byte vectors; host buffers are staged and have no
+ *     alignment rule).  Malformed records are data, not an error: the call returns SUCCESS.
+ *   timing: NOT constant time -- a lane leaves at its first failing test.  Encoded points are
+ *     public, so nothing secret is involved.                                                   */
+/* ------------------------------------------------------------------------------------ */
+typedef enum {
+    MBLS_DECODE_OK = 0,           /* a curve point was written                                   */
+    MBLS_DECODE_IDENTITY = 1,     /* the infinity encoding: the all-zero point was written       */
+    MBLS_DECODE_NONCANONICAL = 2, /* x (G2: a component of x) >= p                               */
+    MBLS_DECODE_NO_POINT = 3,     /* x^3 + b is not a square: no curve point has this x          */
+    /* 4 is left unused: it is MBLS_POINT_OFF_SUBGROUP, which decoding does not test            */
+    MBLS_DECODE_BAD_FLAGS = 5     /* C clear, or I set with S set or with any other bit set      */
+} mbls_decode_status;
+
+eIcicleError mbls_g1_decompress(const uint8_t* bytes, int size, bool points_montgomery, const VecOpsConfig* config,
+                                mbls_g1_affine_t* points, uint8_t* status, uint64_t* n_invalid);
+eIcicleError mbls_g2_decompress(const uint8_t* bytes, int size, bool points_montgomery, const VecOpsConfig* config,
+                                mbls_g2_affine_t* points, uint8_t* status, uint64_t* n_invalid);
+eIcicleError mbls_g1_compress(const mbls_g1_affine_t* points, int size, bool points_montgomery,
+                              const VecOpsConfig* config, uint8_t* bytes);
+eIcicleError mbls_g2_compress(const mbls_g2_affine_t* points, int size, bool points_montgomery,
+                              const VecOpsConfig* config, uint8_t* bytes);
+
+/* ------------------------------------------------------------------------------------ */
 /* library utilities (no reference counterpart; used by the host API, tests and bench)   */
 /* ------------------------------------------------------------------------------------ */
 const char* mbls_version(void);

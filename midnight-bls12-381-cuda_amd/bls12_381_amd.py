@@ -81,6 +81,7 @@ EXPORTED = [
     "bls12_381_g1_scalar_mul", "bls12_381_g1_scalar_mul_glv", "bls12_381_g2_scalar_mul",
     "mbls_g1_scalar_mul", "mbls_g2_scalar_mul", "mbls_g1_ecntt",
     "mbls_g1_check_points", "mbls_g2_check_points",
+    "mbls_g1_decompress", "mbls_g2_decompress", "mbls_g1_compress", "mbls_g2_compress",
 ]
 
 _LIB = None
@@ -131,6 +132,8 @@ def lib():
         "mbls_g1_scalar_mul": [P, P, i32, b, P, P], "mbls_g2_scalar_mul": [P, P, i32, b, P, P],
         "mbls_g1_ecntt": [P, i32, i32, P, P],
         "mbls_g1_check_points": [P, i32, b, P, P, P], "mbls_g2_check_points": [P, i32, b, P, P, P],
+        "mbls_g1_decompress": [P, i32, b, P, P, P, P], "mbls_g2_decompress": [P, i32, b, P, P, P, P],
+        "mbls_g1_compress": [P, i32, b, P, P], "mbls_g2_compress": [P, i32, b, P, P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -318,6 +321,56 @@ def check_points(group, pts, *, points_mont=True, out=None, count=True, stream=N
     check(getattr(lib(), name)(_p(pts), n, bool(points_mont), ctypes.byref(cfg), _p(out),
                                ctypes.byref(cnt) if count else None), name)
     return out, (int(cnt.value) if count else None)
+
+
+# mbls_decode_status (include/bls12_381_mi355x.h): 0 and 1 are valid, >= 2 invalid; 0..3 line up with
+# POINT_*, 4 (POINT_OFF_SUBGROUP) is left unused
+DECODE_OK, DECODE_IDENTITY, DECODE_NONCANONICAL, DECODE_NO_POINT, DECODE_BAD_FLAGS = 0, 1, 2, 3, 5
+
+
+def decompress_points(group, data, *, points_mont=True, out=None, status=None, count=True, stream=None,
+                      is_async=False):
+    """Batch point decompression (mbls_g*_decompress): `data` (n, 48 | 96) uint8 records in the ZCash
+    compressed encoding, numpy (host) or torch (device).  Returns (points, status, n_invalid): points
+    (n, 12 | 24) uint64 affine, Montgomery unless points_mont is False, all-zero for every record
+    whose status is not DECODE_OK; status[i] the first failing test of record i (DECODE_*);
+    n_invalid the number of statuses >= 2, or None for count=False.  Points and status are host
+    numpy arrays by default; `out` (int64 torch) and `status` (uint8 torch) place them, together, on
+    the device (then a call with count=False and is_async does not wait); status=False asks for
+    none.  No subgroup test is made: check_points on the result is the next step."""
+    n, nl = data.shape[0], 12 if group == "g1" else 24
+    assert data.shape[1] == 4 * nl
+    if status is False:
+        status = None
+    elif status is None:
+        if _is_dev(out):
+            import torch
+            status = torch.zeros((n,), dtype=torch.uint8, device=out.device)
+        else:
+            status = np.zeros(n, dtype=np.uint8)
+    if out is None:
+        out = torch_u64((n, nl), device=status.device) if _is_dev(status) else np.zeros((n, nl), dtype=np.uint64)
+    assert status is None or _is_dev(status) == _is_dev(out), "points and status share one placement"
+    cnt = ctypes.c_uint64(0) if count else None
+    cfg = vec_config(is_a_on_device=_is_dev(data), is_result_on_device=_is_dev(out), stream=stream, is_async=is_async)
+    name = "mbls_g1_decompress" if group == "g1" else "mbls_g2_decompress"
+    check(getattr(lib(), name)(_p(data), n, bool(points_mont), ctypes.byref(cfg), _p(out), _p(status),
+                               ctypes.byref(cnt) if count else None), name)
+    return out, status, (int(cnt.value) if count else None)
+
+
+def compress_points(group, pts, *, points_mont=True, out=None, stream=None, is_async=False):
+    """Batch point compression (mbls_g*_compress): `pts` (n, 12 | 24) uint64 affine, Montgomery unless
+    points_mont is False, numpy (host) or torch (device); the all-zero point gives the infinity
+    record.  Returns (n, 48 | 96) uint8, host numpy unless `out` is a device uint8 tensor.  Nothing
+    is validated."""
+    n = pts.shape[0]
+    if out is None:
+        out = np.zeros((n, 48 if group == "g1" else 96), dtype=np.uint8)
+    cfg = vec_config(is_a_on_device=_is_dev(pts), is_result_on_device=_is_dev(out), stream=stream, is_async=is_async)
+    name = "mbls_g1_compress" if group == "g1" else "mbls_g2_compress"
+    check(getattr(lib(), name)(_p(pts), n, bool(points_mont), ctypes.byref(cfg), _p(out)), name)
+    return out
 
 
 def vec_sum(x, out=None, stream=None):
