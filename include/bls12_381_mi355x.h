@@ -220,6 +220,46 @@ eIcicleError vec_sum_cuda(mbls_fr_t* output, const mbls_fr_t* input, int size, c
 eIcicleError bls12_381_batch_inv_cuda(mbls_fr_t* output, const mbls_fr_t* input, int size, const VecOpsConfig* config);
 
 /* ------------------------------------------------------------------------------------ */
+/* Fr prefix scans along a column: the grand product of the permutation and lookup arguments, and
+ * polynomial evaluation with division by X - z (KZG openings).  (No reference counterpart: the
+ * reference computes these on the CPU -- compute_product, eval_polynomial, kate_division -- and
+ * uploads the column afterwards.)
+ *   elements: Montgomery and canonical (< r), in and out; z and init likewise.  init == NULL means
+ *     Montgomery one.
+ *   batch: config->batch_size members (0 counts as 1), row-major, each of `size` elements; z, init,
+ *     total and eval hold one element per member.  columns_batch gives API_NOT_IMPLEMENTED, as
+ *     bls12_381_vector_sum does.
+ *   zero denominators: the inverse of 0 is 0, as in bls12_381_batch_inv_cuda, so a zero in num or
+ *     in den makes every later product of that member 0.
+ *   placement: config->is_a_on_device num and den (or coeffs), is_b_on_device init (or z),
+ *     is_result_on_device output and total (or quotient and eval).  Host buffers are staged through
+ *     the leased scratch context, which also holds the work arrays (no allocation per call once it
+ *     is large enough); a host result makes the call synchronous, otherwise it synchronises unless
+ *     is_async.
+ *   optional outputs: total may be NULL, output may not.  Either of quotient and eval may be NULL,
+ *     not both; quotient == NULL is pure evaluation and writes no vector.
+ *   in place: output may equal num or den, quotient may equal coeffs (the same pointer); any other
+ *     overlap is undefined.
+ *   errors, before any device work: INVALID_POINTER for a null num / coeffs, z, config or a missing
+ *     required output (the vecops' convention); INVALID_ARGUMENT for size == 0 or
+ *     size * batch > 2^26.
+ *   timing: no branch and no address depends on a field value; the denominators go through the
+ *     fixed Fermat chain with mask selects for zeros, as in bls12_381_batch_inv_cuda.            */
+/* ------------------------------------------------------------------------------------ */
+/* out[k*size + i] = init[k] * prod_{j < i} r[k*size + j]   (exclusive; inclusive: j <= i)
+ * r[j] = num[j] * den[j]^-1, or num[j] when den == NULL;  total[k] = init[k] * prod_{all j} r[j] */
+eIcicleError mbls_fr_prefix_product(const mbls_fr_t* num, const mbls_fr_t* den, size_t size, const mbls_fr_t* init,
+                                    bool inclusive, const VecOpsConfig* config, mbls_fr_t* output, mbls_fr_t* total);
+/* quotient[k*size + i] = sum_{j > i} a[k*size + j] * z[k]^(j-i-1)   (so quotient[size-1] = 0)
+ * eval[k] = a[k*size] + z[k] * quotient[k*size] = p_k(z[k]);   p_k = quotient_k * (X - z[k]) + eval[k] */
+eIcicleError mbls_fr_poly_divide_linear(const mbls_fr_t* coeffs, size_t size, const mbls_fr_t* z,
+                                        const VecOpsConfig* config, mbls_fr_t* quotient, mbls_fr_t* eval);
+/* host only, no device work: out[0] = K (elements per thread), out[1] = tile elements,
+ * out[2] = workgroups launched per member for `size`, out[3] = elements per workgroup span.
+ * size in 1..2^26. */
+eIcicleError mbls_fr_scan_geometry(size_t size, int32_t* out);
+
+/* ------------------------------------------------------------------------------------ */
 /* batch point-form conversions, reference point_ops.cu:759 / :844 / :924 (exported there as
  * extern "C").  Montgomery in, Montgomery out; Jacobian projective (x = X/Z^2, y = Y/Z^3).
  * affine_to_projective: (x, y) -> (x, y, 1), identity (0, 0) -> (0, 1, 0).

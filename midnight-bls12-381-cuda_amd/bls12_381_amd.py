@@ -82,6 +82,7 @@ EXPORTED = [
     "mbls_g1_scalar_mul", "mbls_g2_scalar_mul", "mbls_g1_ecntt",
     "mbls_g1_check_points", "mbls_g2_check_points",
     "mbls_g1_decompress", "mbls_g2_decompress", "mbls_g1_compress", "mbls_g2_compress",
+    "mbls_fr_prefix_product", "mbls_fr_poly_divide_linear", "mbls_fr_scan_geometry",
 ]
 
 _LIB = None
@@ -134,6 +135,8 @@ def lib():
         "mbls_g1_check_points": [P, i32, b, P, P, P], "mbls_g2_check_points": [P, i32, b, P, P, P],
         "mbls_g1_decompress": [P, i32, b, P, P, P, P], "mbls_g2_decompress": [P, i32, b, P, P, P, P],
         "mbls_g1_compress": [P, i32, b, P, P], "mbls_g2_compress": [P, i32, b, P, P],
+        "mbls_fr_prefix_product": [P, P, sz, P, b, P, P, P], "mbls_fr_poly_divide_linear": [P, sz, P, P, P, P],
+        "mbls_fr_scan_geometry": [sz, P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -398,6 +401,72 @@ def batch_inv(x, out, stream=None):
     cfg = vec_config(stream=stream)
     check(lib().bls12_381_batch_inv_cuda(_p(out), _p(x), x.shape[0], ctypes.byref(cfg)), "bls12_381_batch_inv_cuda")
     return out
+
+
+# ----------------------------------------------------------------------------- scans
+GEOMETRY_FIELDS = ("K", "tile", "groups", "span")
+
+
+def scan_geometry(n):
+    """the launch geometry of the scans for a member of n elements (mbls_fr_scan_geometry; host
+    only): dict of GEOMETRY_FIELDS -- elements per thread, elements per tile, workgroups, elements
+    per workgroup span"""
+    out = (ctypes.c_int32 * len(GEOMETRY_FIELDS))()
+    check(lib().mbls_fr_scan_geometry(n, out), "mbls_fr_scan_geometry")
+    return dict(zip(GEOMETRY_FIELDS, list(out)))
+
+
+def _like(ref, rows):
+    """(rows, 4) uint64 storage placed as `ref` is: a device tensor or a host array"""
+    return torch_u64((rows, 4), device=ref.device) if _is_dev(ref) else np.zeros((rows, 4), dtype=np.uint64)
+
+
+def prefix_product(num, den=None, *, init=None, inclusive=False, batch=1, out=None, total=False, stream=None,
+                   is_async=False):
+    """Grand product (mbls_fr_prefix_product): out[i] = init * prod_{j < i} num[j] / den[j] per batch
+    member (inclusive: j <= i), 1 / 0 = 0.  num, den (batch*n, 4) uint64 Montgomery, both numpy
+    (host) or both torch (device); init (batch, 4), default Montgomery one.  Returns out, a host
+    array unless `out` is a device tensor (`out` may be num or den); with total=True, or a
+    (batch, 4) buffer placed as `out`, returns (out, total), total[k] = init[k] * all of member k."""
+    n = num.shape[0] // batch
+    assert den is None or _is_dev(den) == _is_dev(num), "num and den share one placement"
+    if out is None:
+        out = np.zeros((num.shape[0], 4), dtype=np.uint64)
+    if total is True:
+        total = _like(out, batch)
+    elif total is False:
+        total = None
+    assert total is None or _is_dev(total) == _is_dev(out), "out and total share one placement"
+    cfg = vec_config(is_a_on_device=_is_dev(num), is_b_on_device=_is_dev(init), is_result_on_device=_is_dev(out),
+                     is_async=is_async, stream=stream, batch_size=batch)
+    check(lib().mbls_fr_prefix_product(_p(num), _p(den), n, _p(init), bool(inclusive), ctypes.byref(cfg), _p(out),
+                                       _p(total)), "mbls_fr_prefix_product")
+    return out if total is None else (out, total)
+
+
+def poly_divide_linear(coeffs, z, *, batch=1, out=None, quotient=True, eval=True, stream=None, is_async=False):
+    """Division by X - z with remainder (mbls_fr_poly_divide_linear): per batch member p = q * (X - z)
+    + p(z).  coeffs (batch*n, 4) uint64 Montgomery, lowest degree first, z (batch, 4), each numpy
+    (host) or torch (device).  Returns (q, p_z): q (batch*n, 4) with q[n-1] = 0, `out` when given
+    (`out` may be coeffs), None for quotient=False (pure evaluation, no vector is written); p_z
+    (batch, 4), `eval` when it is a buffer, None for eval=False.  Both are placed alike: on the
+    device when `out` (or, without a quotient, `eval`) is a device tensor, else on the host."""
+    n = coeffs.shape[0] // batch
+    if not quotient:
+        out = None
+    elif out is None:
+        out = _like(None if isinstance(eval, bool) else eval, coeffs.shape[0])
+    if eval is True:
+        eval = _like(out, batch) if out is not None else np.zeros((batch, 4), dtype=np.uint64)
+    elif eval is False:
+        eval = None
+    assert out is None or eval is None or _is_dev(out) == _is_dev(eval), "quotient and eval share one placement"
+    cfg = vec_config(is_a_on_device=_is_dev(coeffs), is_b_on_device=_is_dev(z),
+                     is_result_on_device=_is_dev(out if out is not None else eval), is_async=is_async, stream=stream,
+                     batch_size=batch)
+    check(lib().mbls_fr_poly_divide_linear(_p(coeffs), n, _p(z), ctypes.byref(cfg), _p(out), _p(eval)),
+          "mbls_fr_poly_divide_linear")
+    return out, eval
 
 
 # ----------------------------------------------------------------------------- NTT

@@ -352,6 +352,22 @@ MBLS_DEV void store(void* p, const Fp<C>& a) {
     for (int i = 0; i < C::N / 4; ++i) q[i] = make_uint4(a.v[4 * i], a.v[4 * i + 1], a.v[4 * i + 2], a.v[4 * i + 3]);
 }
 
+// Constant-time selection for witness-derived Fr values (batch inversion, the scans): c ? a : b
+// with a full-word mask (no data-dependent branch, whatever the compiler would make of
+// a ternary); the zero test is an OR-reduction, not an early-exit compare
+MBLS_DEV uint32_t zero_mask(const Fr& x) {
+    uint32_t o = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o |= x.v[i];
+    return 0u - (uint32_t)(o == 0u);  // all ones iff x == 0
+}
+MBLS_DEV Fr fr_select(uint32_t mask, const Fr& a, const Fr& b) {
+    Fr r;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.v[i] = (a.v[i] & mask) | (b.v[i] & ~mask);
+    return r;
+}
+
 // non-temporal streaming variants (data touched once)
 template <class C>
 MBLS_DEV Fp<C> load_nt(const void* p) {

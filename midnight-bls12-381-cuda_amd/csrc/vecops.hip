@@ -107,21 +107,8 @@ __global__ __launch_bounds__(256) void k_sum_partial(uint8_t* __restrict__ out, 
 // The inputs can be witness-derived scalars, so this path keeps the reference's constant-time
 // shape: the chunk inversion is the fixed Fermat chain a^(r-2) (field.cuh:735-900; not the
 // variable-time binary GCD of inv()), and zero inputs are handled by selects, not branches.
+// (zero_mask / fr_select, mbls_field.hpp)
 static constexpr int INV_CHUNK = 64;
-// c ? a : b with a full-word mask (no data-dependent branch, whatever the compiler
-// would make of a ternary); the zero test is an OR-reduction, not an early-exit compare
-MBLS_DEV uint32_t zero_mask(const Fr& x) {
-    uint32_t o = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) o |= x.v[i];
-    return 0u - (uint32_t)(o == 0u);  // all ones iff x == 0
-}
-MBLS_DEV Fr fr_select(uint32_t mask, const Fr& a, const Fr& b) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r.v[i] = (a.v[i] & mask) | (b.v[i] & ~mask);
-    return r;
-}
 __global__ __launch_bounds__(256) void k_batch_inv(uint8_t* __restrict__ out, const uint8_t* __restrict__ in,
                                                    size_t n) {
     const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
