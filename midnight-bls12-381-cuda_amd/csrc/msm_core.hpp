@@ -25,7 +25,9 @@
 //                     weight 1 and the last level's output IS the window sum (no scalar
 //                     multiplications, no per-level tree sums, no window Horner).  Lane levels
 //                     over raw XYZZ records: k_reduce_scaled_r28x (G1) / _r28px (G2); row and
-//                     wave levels: k_reduce_scaled<F, MODE>, narrow ones k_reduce_tree4.
+//                     wave levels: k_reduce_scaled<F, MODE>, narrow ones k_reduce_tree4.  G1's lane
+//                     level 0 and row level 1 run as one launch, level 1 as a lane-arithmetic
+//                     tree over eight lanes per segment (k_reduce_tree8_r28x).
 //   7. k_final        fold over windows: sum_w 2^(c w) G_w; k_final_icicle adds ICICLE's
 //                     (x, y, 1) normalisation in the same launch.
 // Precompute factor F (bases table = F blocks of n bases, block f = 2^(c*Wg*f) * P) folds
@@ -987,6 +989,26 @@ __global__ __launch_bounds__(256) void k_reduce_scaled(const uint8_t* __restrict
 // G1's lane-mode level 0 over raw XYZZ buckets (buckets_xyzz, no U) in radix 2^28: the chain of
 // k_reduce_scaled with add-2008-s (r28::xadd, 12M + 2S) for its two additions per step, the
 // outputs converted once.  Bucket t - 1 is loaded before bucket t is added.
+// One lane's chain over buckets [k0, k1) of the window at record `base`: S = sum (t - k0 + off) V_t
+// and, with `scale`, R = 2^seg_log sum V_t (else the plain sum).  An empty range leaves both the
+// identity, and a doubled identity stays exactly zz = 0.
+MBLS_DEV void r28x_chain(const uint8_t* __restrict__ V, uint32_t base, uint32_t k0, uint32_t k1, uint32_t seg_log,
+                         int off, bool scale, r28::X28& R, r28::X28& S) {
+    R = r28::X28::inf(), S = r28::X28::inf();
+    if (k1 <= k0) return;
+    uint32_t nw[56];  // bucket t - 1, loaded while bucket t is added (one wave per SIMD: nothing else hides it)
+    load_raw56(V, (size_t)(base + k1 - 1) * 224, nw);
+    for (uint32_t t = k1; t-- > k0;) {
+        uint32_t cw[56];
+#pragma unroll
+        for (int i = 0; i < 56; ++i) cw[i] = nw[i];
+        if (t > k0) load_raw56(V, (size_t)(base + t - 1) * 224, nw);
+        xadd_raw(R, cw);                                                                   // R += V_t
+        if ((t - k0) + off != 0 && !R.is_inf()) r28::xadd(S, R.x, R.y, R.zz, R.zzz);  // S += R
+    }
+    if (scale && !R.is_inf())
+        for (uint32_t k = 0; k < seg_log; ++k) r28::xdbl(R);
+}
 template <class F>  // F = Fq only
 __global__ __launch_bounds__(256) void k_reduce_scaled_r28x(const uint8_t* __restrict__ V, uint32_t m_in,
                                                             uint32_t seg_log, int Wg, int off,
@@ -999,24 +1021,103 @@ __global__ __launch_bounds__(256) void k_reduce_scaled_r28x(const uint8_t* __res
     const uint32_t w = tid / m_out, q = tid % m_out;
     const uint32_t k0 = q << seg_log;
     const uint32_t k1 = min(k0 + seg, m_in);  // exclusive
-    const uint32_t base = w * m_in;
-    r28::X28 R = r28::X28::inf(), S = r28::X28::inf();
-    uint32_t nw[56];  // bucket t - 1, loaded while bucket t is added (one wave per SIMD: nothing else hides it)
-    load_raw56(V, (size_t)(base + k1 - 1) * 224, nw);
-    for (uint32_t t = k1; t-- > k0;) {
-        uint32_t cw[56];
-#pragma unroll
-        for (int i = 0; i < 56; ++i) cw[i] = nw[i];
-        if (t > k0) load_raw56(V, (size_t)(base + t - 1) * 224, nw);
-        xadd_raw(R, cw);                                                                   // R += V_t
-        if ((t - k0) + off != 0 && !R.is_inf()) r28::xadd(S, R.x, R.y, R.zz, R.zzz);  // S += R
-    }
-    if (Vout) {
-        if (!R.is_inf())
-            for (uint32_t k = 0; k < seg_log; ++k) r28::xdbl(R);
-        store_jac28(Vout, tid, r28::x_to_jac(R));
-    }
+    r28::X28 R, S;
+    r28x_chain(V, w * m_in, k0, k1, seg_log, off, Vout != nullptr, R, S);
+    if (Vout) store_jac28(Vout, tid, r28::x_to_jac(R));
     store_jac28(Uout, tid, r28::x_to_jac(S));
+}
+
+// G1's level 1 (row plan: segments of 8, off = 0) as a tree in lane arithmetic.  A segment's
+// outputs are linear in its inputs,
+//   U' = sum_j U_j + sum_j j V_j = sum U + T0 + 2 T1 + 4 T2   (T_b: the V_j with bit b of j set)
+//   V' = 8 sum_j V_j,
+// so eight adjacent lanes evaluate them in six passes of one r28::xadd and / or one r28::xdbl per
+// lane instead of the chain's 27 dependent row-sliced operations.  Lane j enters with V_j, U_j
+// (the identity past the level's end); X is its running value, operands cross lanes as the 56 raw
+// limbs by ds_bpermute (no LDS, no barrier).  P_i = V_2i + V_2i+1, Q_i = U_2i + U_2i+1:
+//   pass 0 add: lane 2i: P_i = V_2i + V_2i+1                lane 2i+1: Q_i = U_2i+1 + U_2i
+//   pass 1 add: 0: P0 + P1   2: T1 = P1 + P3   4: T2 = P2 + P3   1: Q0 + Q1   5: Q2 + Q3
+//               3: V3 + V1   7: V7 + V5
+//   pass 2 add: 0: SV = (P0 + P1) + T2   2: T1 + T2   3: T0 = (V3 + V1) + (V7 + V5)   1: SU
+//   pass 3 add: 2: W = (T1 + T2) + T2    1: E = SU + T0          dbl: 0: 2 SV
+//   pass 4                                                       dbl: 2: 2 W    0: 4 SV
+//   pass 5 add: 1: U' = E + 2 W                                  dbl: 0: V' = 8 SV
+// Doublings share only passes 3 and 5 with additions (a wave holding both issues both bodies).
+// Every addition is xadd with its identity / equal / opposite branches -- the tree meets operand
+// coincidences the chain never did (T1 = T2, E = 2 W, V_j = +-V_k) -- and the identity is never
+// doubled, so it stays exactly zz = 0 (tests/reduce_tree_model.py restates the sites).
+// Lanes 0 and 1 convert once and store V', U' as the Jacobian words the wave levels read.
+MBLS_DEV r28::X28 lane_fetch(const r28::X28& p, uint32_t src_byte) {
+    r28::X28 r;
+#pragma unroll
+    for (int i = 0; i < r28::NL; ++i) {
+        r.x.l[i] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)src_byte, (int)p.x.l[i]);
+        r.y.l[i] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)src_byte, (int)p.y.l[i]);
+        r.zz.l[i] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)src_byte, (int)p.zz.l[i]);
+        r.zzz.l[i] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)src_byte, (int)p.zzz.l[i]);
+    }
+    return r;
+}
+// sel: 0 a, 1 b, 2 c
+MBLS_DEV r28::X28 lane_pick(uint32_t sel, const r28::X28& a, const r28::X28& b, const r28::X28& c) {
+    r28::X28 r;
+#pragma unroll
+    for (int i = 0; i < r28::NL; ++i) {
+        r.x.l[i] = sel == 0 ? a.x.l[i] : sel == 1 ? b.x.l[i] : c.x.l[i];
+        r.y.l[i] = sel == 0 ? a.y.l[i] : sel == 1 ? b.y.l[i] : c.y.l[i];
+        r.zz.l[i] = sel == 0 ? a.zz.l[i] : sel == 1 ? b.zz.l[i] : c.zz.l[i];
+        r.zzz.l[i] = sel == 0 ? a.zzz.l[i] : sel == 1 ? b.zzz.l[i] : c.zzz.l[i];
+    }
+    return r;
+}
+// All 64 lanes of the wave call it together (the fetches read the other lanes' registers).
+// Returns lane 0's V' and lane 1's U' of each group of eight.
+MBLS_DEV r28::X28 reduce_tree8(const r28::X28& V, const r28::X28& U) {
+    const uint32_t lane = __lane_id(), j = lane & 7;
+    r28::X28 X = r28::X28::inf();
+#pragma unroll 1
+    for (int p = 0; p < 6; ++p) {
+        // per pass: the lanes that add / double (bit j), the lane each adding lane fetches from
+        // (nibble j), what a lane fetches from holds out and what an adding lane adds to (two
+        // bits per lane: 0 X, 1 V, 2 U)
+        const uint32_t addm = (uint32_t)(0x0200060fbfffull >> (8 * p)) & 0xffu;
+        const uint32_t dblm = (uint32_t)(0x010501000000ull >> (8 * p)) & 0xffu;
+        if (addm) {  // wave-uniform
+            const uint32_t src = p == 0 ? 0x67452301u : p == 1 ? 0x56761632u : p == 2 ? 0x76547454u
+                                 : p == 3 ? 0x76543430u : 0x76543220u;
+            const uint32_t pub = p == 0 ? 0x6666u : p == 1 ? 0x0404u : 0u;
+            const uint32_t own = p == 0 ? 0x9999u : p == 1 ? 0x4040u : 0u;
+            const r28::X28 out = lane_pick((pub >> (2 * j)) & 3u, X, V, U);
+            X = lane_pick((own >> (2 * j)) & 3u, X, V, U);
+            const r28::X28 b = lane_fetch(out, ((lane & ~7u) | ((src >> (4 * j)) & 7u)) << 2);
+            if (((addm >> j) & 1u) && !b.is_inf()) r28::xadd(X, b.x, b.y, b.zz, b.zzz);
+        }
+        if (((dblm >> j) & 1u) && !X.is_inf()) r28::xdbl(X);
+    }
+    return X;
+}
+// Levels 0 and 1 in one launch: lane (segment, j) first runs the level-0 chain whose outputs are
+// the segment's inputs j (V: the raw bucket sums, m0 per window, level-0 segments of 2^seg0_log),
+// keeps them in registers and goes straight into the tree -- no hand-over through memory, one
+// launch fewer (the plan still counts two levels).  m_in: level 1's inputs per window.  No lane
+// returns before the tree.
+template <class F>  // F = Fq only
+__global__ __launch_bounds__(256) void k_reduce_tree8_r28x(const uint8_t* __restrict__ V, uint32_t m0, uint32_t seg0_log,
+                                                           uint32_t m_in, int Wg, uint8_t* __restrict__ Vout,
+                                                           uint8_t* __restrict__ Uout) {
+    MBLS_TAIL_PRIO();
+    const uint32_t m_out = (m_in + 7) >> 3;
+    const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t w = tid / (8 * m_out), q = tid % (8 * m_out);  // q: the input's index in its window
+    const bool live = w < (uint32_t)Wg && q < m_in;
+    r28::X28 Vj, Uj;
+    const uint32_t k0 = q << seg0_log;
+    const uint32_t k1 = live ? min(k0 + (1u << seg0_log), m0) : k0;  // an empty range: the identity
+    r28x_chain(V, w * m0, k0, k1, seg0_log, 1, true, Vj, Uj);
+    const r28::X28 X = reduce_tree8(Vj, Uj);
+    const uint32_t j = tid & 7;
+    uint8_t* out = j == 0 ? Vout : Uout;
+    if (w < (uint32_t)Wg && j < 2 && out) store_jac28(out, tid >> 3, r28::x_to_jac(X));
 }
 
 // the same over raw pair-sliced XYZZ records (G2): one chain per lane pair; a lane level after
@@ -1407,6 +1508,14 @@ inline bool buckets_xyzz(const MsmPlan& P) {
 }
 // a level output record's bytes: raw pair XYZZ (448) when G2 chains lane levels (they take raw
 // records from the level before), else Jacobian
+// G1's row level 1 of 8-input segments behind a lane level 0 runs as the lane-arithmetic tree
+// (k_reduce_tree8_r28x).  Every other row level keeps k_reduce_scaled<F, MODE_ROW>: a row level 0
+// (off = 1, the c = 13 plans), other segment lengths, G2.
+template <class F>
+inline bool tree8_level1(const MsmPlan& P) {
+    return std::is_same<F, Fq>::value && buckets_xyzz<F>(P) && P.levels > 1 &&
+           P.mode[1] == MODE_ROW && P.seg_log[1] == 3;
+}
 template <class F>
 inline size_t level_bytes(const MsmPlan& P) {
     return (std::is_same<F, Fq2>::value && buckets_xyzz<F>(P) && P.levels > 1 && P.mode[1] == MODE_LANE)
@@ -1737,8 +1846,19 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
             if (!raw_in) {
                 launch_reduce_scaled<F>(P.mode[l], V, U, m_in, P.seg_log[l], P.Wg, l == 0 ? 1 : 0, Vo, Uo, chains, st);
             } else if constexpr (std::is_same<F, Fq>::value) {  // lane level 0
-                hipLaunchKernelGGL((k_reduce_scaled_r28x<F>), dim3((chains + 255) / 256), dim3(256), 0, st, V, m_in,
-                                   P.seg_log[0], P.Wg, 1, Vo, Uo);
+                if (tree8_level1<F>(P)) {
+                    // levels 0 and 1 in one launch: the lane keeps its level-0 outputs for the tree
+                    const uint32_t m1 = P.level_m[1], mo1 = (m1 + 7) / 8;
+                    const bool last1 = P.levels == 2;
+                    Vo = last1 ? nullptr : vb[1];
+                    Uo = last1 ? S.windows : ub[1];
+                    hipLaunchKernelGGL((k_reduce_tree8_r28x<F>), dim3((8 * mo1 * (uint32_t)P.Wg + 255) / 256), dim3(256),
+                                       0, st, V, m_in, P.seg_log[0], m1, P.Wg, Vo, Uo);
+                    ++l;
+                } else {
+                    hipLaunchKernelGGL((k_reduce_scaled_r28x<F>), dim3((chains + 255) / 256), dim3(256), 0, st, V, m_in,
+                                       P.seg_log[0], P.Wg, 1, Vo, Uo);
+                }
                 raw_in = false;
             } else {  // G2: lane level 0, or the lane levels after it
                 const bool raw_out = !last && P.mode[l + 1] == MODE_LANE;

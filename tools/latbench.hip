@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include "mbls_curve.hpp"
 #include "mbls_fips.hpp"
+#include "mbls_fq28.hpp"
 #include "mbls_rowfield.hpp"
 #include "mbls_wavepoint.hpp"
 
@@ -132,6 +133,45 @@ __global__ __launch_bounds__(64) void k_binv_part(uint32_t* out, const uint32_t*
     out[threadIdx.x] = o;
 }
 
+// lane-mode XYZZ point operations (radix 2^28) at the shape of the lane reduction levels: one chain
+// per lane, 256-thread workgroups, 1024 waves (one per SIMD).  OP 0: r28::xadd, 1: r28::xdbl.
+template <int OP>
+__global__ __launch_bounds__(256) void k_r28(uint32_t* out, const uint32_t* in, int n) {
+    r28::X28 a, q;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    for (int i = 0; i < r28::NL; ++i) {
+        a.x.l[i] = (in[i] + t) & r28::MASK, a.y.l[i] = in[14 + i] & r28::MASK;
+        a.zz.l[i] = in[28 + i] & r28::MASK, a.zzz.l[i] = in[42 + i] & r28::MASK;
+        q.x.l[i] = in[40 + i] & r28::MASK, q.y.l[i] = in[54 + i] & r28::MASK;
+        q.zz.l[i] = in[68 + i] & r28::MASK, q.zzz.l[i] = in[82 + i] & r28::MASK;
+    }
+    a.x.l[13] &= 0xffff, a.y.l[13] &= 0xffff, a.zz.l[13] &= 0xffff, a.zzz.l[13] &= 0xffff;
+    q.x.l[13] &= 0xffff, q.y.l[13] &= 0xffff, q.zz.l[13] &= 0xffff, q.zzz.l[13] &= 0xffff;
+    for (int i = 0; i < n; ++i) {
+        if constexpr (OP == 0) r28::xadd(a, q.x, q.y, q.zz, q.zzz);
+        if constexpr (OP == 1) r28::xdbl(a);
+    }
+    uint32_t o = 0;
+    for (int i = 0; i < r28::NL; ++i) o ^= a.x.l[i] ^ a.y.l[i] ^ a.zz.l[i] ^ a.zzz.l[i];
+    out[t] = o;
+}
+
+template <class K>
+static void run_grid(const char* name, K kern, int blocks, int threads, uint32_t* out, const uint32_t* in, int n) {
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0));
+    CK(hipEventCreate(&e1));
+    hipLaunchKernelGGL(kern, blocks, threads, 0, 0, out, in, 4);
+    CK(hipDeviceSynchronize());
+    CK(hipEventRecord(e0));
+    hipLaunchKernelGGL(kern, blocks, threads, 0, 0, out, in, n);
+    CK(hipEventRecord(e1));
+    CK(hipEventSynchronize(e1));
+    float ms;
+    CK(hipEventElapsedTime(&ms, e0, e1));
+    printf("%-28s %8.3f us/op  (%d ops, %.3f ms, %d waves)\n", name, ms * 1e3 / n, n, ms, blocks * threads / 64);
+}
+
 template <class K>
 static void run(const char* name, K kern, uint32_t* out, const uint32_t* in, int n) {
     hipEvent_t e0, e1;
@@ -194,5 +234,11 @@ int main() {
     run("wave jadd", k_wave<1>, out, in, 2000);
     run("row jac_dbl", k_wave<2>, out, in, 2000);
     run("row jac_add", k_wave<3>, out, in, 2000);
+    uint32_t* wide;
+    CK(hipMalloc(&wide, 4 * 256 * 256));
+    run_grid("lane r28 xadd, 1 wave/SIMD", k_r28<0>, 256, 256, wide, in, 400);
+    run_grid("lane r28 xdbl, 1 wave/SIMD", k_r28<1>, 256, 256, wide, in, 400);
+    run_grid("lane r28 xadd, one wave", k_r28<0>, 1, 64, wide, in, 400);
+    run_grid("lane r28 xdbl, one wave", k_r28<1>, 1, 64, wide, in, 400);
     return 0;
 }
