@@ -511,6 +511,18 @@ eIcicleError bls12_381_vector_sum(const mbls_fr_t* a, size_t size, const VecOpsC
  * group: 1 = G1, 2 = G2.  Diagnostics (tests/test_plan.py, tools/). */
 eIcicleError mbls_msm_plan(int group, int msm_size, const MSMConfig* config, int32_t* out);
 
+/* The bucket reduction's kernel schedule of that plan (plan_levels; host only, no device work,
+ * the argument checks of mbls_msm_plan).  *count = the words of the answer, 2 + 7 x levels; with
+ * capacity (the int32 words `out` holds) below that nothing else is written and the call returns
+ * INVALID_ARGUMENT.  out[0] = bucket record format (0 Jacobian words, 1 raw XYZZ
+ * limbs), out[1] = bytes of a level record, then per level l at out[2 + 7 l ..]: kernel (0
+ * k_reduce_scaled, the generic chain in the level's mode; 1 k_reduce_tree4; 2 k_reduce_scaled_r28x;
+ * 3 k_reduce_tree8_r28x; 4 k_reduce_scaled_r28px), index of the launch the level belongs to (the
+ * tree8 launch covers two levels), mode (0 lane, 1 row, 2 wave), log2 of the segment length, inputs
+ * per window, input record format, output record format.  Diagnostics (tests/test_plan.py). */
+eIcicleError mbls_msm_reduce_plan(int group, int msm_size, const MSMConfig* config, int32_t* out, int capacity,
+                                  int32_t* count);
+
 /* Stage profiler (tracing): hipEvent pairs recorded on the caller's
  * stream around each pipeline stage ("msm.accumulate", "ntt.pass", ...) when enabled
  * (or MBLS_PROFILE=1).  read() synchronises the recorded events and returns, per stage,

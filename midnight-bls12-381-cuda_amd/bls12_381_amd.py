@@ -77,7 +77,7 @@ EXPORTED = [
     "mbls_release_stream", "mbls_release_scratch", "mbls_scratch_stats",
     "mbls_g1_msm_multi_device", "mbls_g2_msm_multi_device", "bls12_381_vector_sum",
     "bls12_381_g1_affine_to_projective", "bls12_381_g1_projective_to_affine", "bls12_381_g2_projective_to_affine",
-    "mbls_msm_plan", "mbls_msm_accumulate_event", "mbls_msm_accumulate_event_drop", "mbls_msm_precompute_strict",
+    "mbls_msm_plan", "mbls_msm_reduce_plan", "mbls_msm_accumulate_event", "mbls_msm_accumulate_event_drop", "mbls_msm_precompute_strict",
     "bls12_381_g1_scalar_mul", "bls12_381_g1_scalar_mul_glv", "bls12_381_g2_scalar_mul",
     "mbls_g1_scalar_mul", "mbls_g2_scalar_mul", "mbls_g1_ecntt",
     "mbls_g1_check_points", "mbls_g2_check_points",
@@ -125,7 +125,7 @@ def lib():
         "bls12_381_vector_sum": [P, sz, P, P],
         "bls12_381_g1_affine_to_projective": [P, i32, P, P], "bls12_381_g1_projective_to_affine": [P, i32, P, P],
         "bls12_381_g2_projective_to_affine": [P, i32, P, P],
-        "mbls_msm_plan": [i32, i32, P, P],
+        "mbls_msm_plan": [i32, i32, P, P], "mbls_msm_reduce_plan": [i32, i32, P, P, i32, P],
         "mbls_msm_accumulate_event": [P, P], "mbls_msm_accumulate_event_drop": [P],
         "mbls_msm_precompute_strict": [i32],
         "bls12_381_g1_scalar_mul": [P, P, i32, P, P], "bls12_381_g1_scalar_mul_glv": [P, P, i32, P, P],
@@ -225,6 +225,28 @@ def msm_plan(group, n, **cfg):
     c = msm_config(**cfg)
     check(lib().mbls_msm_plan(1 if group == "g1" else 2, n, ctypes.byref(c), out), "msm_plan")
     return dict(zip(PLAN_FIELDS, list(out)))
+
+
+REDUCE_KERNELS = ("chain", "tree4", "r28x", "tree8", "r28px")  # the library's RedKernel ids
+REDUCE_MODES = ("lane", "row", "wave")
+REDUCE_LEVEL_FIELDS = ("kernel", "launch", "mode", "seg_log", "m_in", "raw_in", "raw_out")
+
+
+def msm_reduce_plan(group, n, **cfg):
+    """the bucket reduction's kernel schedule of msm_plan(group, n, **cfg) (mbls_msm_reduce_plan;
+    host only): dict(bucket_raw, level_bytes, levels = [dict of REDUCE_LEVEL_FIELDS]), kernel and
+    mode by name"""
+    out = (ctypes.c_int32 * 128)()
+    cnt = ctypes.c_int32(0)
+    c = msm_config(**cfg)
+    check(lib().mbls_msm_reduce_plan(1 if group == "g1" else 2, n, ctypes.byref(c), out, len(out), ctypes.byref(cnt)),
+          "msm_reduce_plan")
+    levels = []
+    for k in range(2, cnt.value, len(REDUCE_LEVEL_FIELDS)):
+        lv = dict(zip(REDUCE_LEVEL_FIELDS, out[k:k + len(REDUCE_LEVEL_FIELDS)]))
+        lv["kernel"], lv["mode"] = REDUCE_KERNELS[lv["kernel"]], REDUCE_MODES[lv["mode"]]
+        levels.append(lv)
+    return dict(bucket_raw=out[0], level_bytes=out[1], levels=levels)
 
 
 def ntt_config(**kw):

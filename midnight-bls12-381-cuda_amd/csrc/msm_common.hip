@@ -1,5 +1,6 @@
-// msm_common.hip -- group-independent MSM stages: plan, signed-digit decomposition, scans,
-// counting-sort scatter, chunking, synthetic scalars.
+// msm_common.hip -- group-independent MSM stages: plan and reduction schedule, endomorphism
+// splits, signed digits and the two sorts (partitioned counting sort for c <= 16; atomic ranks,
+// scan and scatter for c > 16), chunking, synthetic scalars.
 //
 // Reference: get_optimal_c (msm.cuh:115-133), compute_bucket_indices_kernel
 // (msm_kernels.cu:69-143), histogram (:224-256), cub ExclusiveSum / SortPairs (:748-781).
@@ -106,7 +107,7 @@ eIcicleError make_plan(long long n, const MSMConfig* cfg, MsmPlan& p, int endo) 
     const bool slot0 = F > 1 && !p.prepared && !shift_plan(n, F, endo);
     // Endomorphism split (no precomputed table, wide scalars):
     //   G1 GLV: two half-width digit streams, |m| < 2^127;
-    //   G2 psi: four quarter-width streams, |m| < 2^63 (tiled digits only, c <= 16; worth it
+    //   G2 psi: four quarter-width streams, |m| < 2^63 (partitioned sort only, c <= 16; worth it
     //   only for wide scalars: plain needs ceil((bits+1)/c) windows of n, psi 4 x ceil(64/c)).
     const bool wide = endo == 2 ? bits > 128 : bits > 192;
     const int split = endo > 1 && (p.prepared || slot0 || (F == 1 && wide)) ? endo : 1;
@@ -178,6 +179,25 @@ extern "C" eIcicleError mbls_msm_plan(int group, int msm_size, const MSMConfig* 
     return MBLS_SUCCESS;
 }
 
+extern "C" eIcicleError mbls_msm_reduce_plan(int group, int msm_size, const MSMConfig* config, int32_t* out,
+                                             int capacity, int32_t* count) {
+    if (!config || !out || !count) return MBLS_INVALID_POINTER;
+    if ((group != 1 && group != 2) || msm_size < 0) return MBLS_INVALID_ARGUMENT;
+    mbls::MsmPlan p;
+    const eIcicleError er = mbls::make_plan(msm_size > 0 ? msm_size : 1, config, p, group == 1 ? 2 : 4);
+    if (er != MBLS_SUCCESS) return er;
+    *count = 2 + 7 * p.levels;
+    if (capacity < *count) return MBLS_INVALID_ARGUMENT;
+    out[0] = p.bucket_raw ? 1 : 0;
+    out[1] = (int32_t)p.level_bytes;
+    for (int l = 0; l < p.levels; ++l) {
+        const int32_t v[7] = {p.launch[p.launch_of[l]].kernel, p.launch_of[l], p.mode[l], p.seg_log[l],
+                              (int32_t)p.level_m[l], p.raw_in[l], p.raw_out[l]};
+        for (int k = 0; k < 7; ++k) out[2 + 7 * l + k] = v[k];
+    }
+    return MBLS_SUCCESS;
+}
+
 namespace mbls {
 
 // Reduction levels for launches over Wl windows: level 0 has B inputs, level l divides by
@@ -226,6 +246,34 @@ namespace mbls {
 #ifndef MBLS_LANE_MIN_G2
 #define MBLS_LANE_MIN_G2 8192u
 #endif
+// row levels with fewer segments than this run one segment per wave.  An Fq2 row-sliced addition
+// is three row products per Fq2 product in series, so G2 switches to the wave layout (the three
+// spread over rows) at more segments (8192, with G2 row segments of 8; 4096 measured 1.75 ms of
+// G2 reduction at 2^20, 8192 and 16384 1.64 ms)
+#ifndef MBLS_WAVE_MIN
+#define MBLS_WAVE_MIN 2048u
+#endif
+#ifndef MBLS_WAVE_MIN_G2
+#define MBLS_WAVE_MIN_G2 8192u
+#endif
+// wave-layout levels of 4-input segments with at most this many segments run as trees of 4
+// waves (k_reduce_tree4; 0 disables)
+#ifndef MBLS_TREE_MAX
+#define MBLS_TREE_MAX 512u
+#endif
+// The one place that decides the reduction's schedule.  First the levels (mode, segment length,
+// inputs and outputs per window), then what msm_device launches for them and in which record
+// format each level reads and writes:
+//   * a lane level 0 makes the bucket sums raw XYZZ records (k_bucket_small stores them so);
+//   * G1 runs that level as k_reduce_scaled_r28x -- fused with level 1 as k_reduce_tree8_r28x when
+//     level 1 is a row level of 8-input segments (the tree's shape); its outputs are Jacobian;
+//   * G2 runs its lane levels over raw records as k_reduce_scaled_r28px, which writes raw records
+//     exactly when the next level is a lane level too;
+//   * a wave level of 4-input segments at weight offset 0 with <= MBLS_TREE_MAX chains runs as
+//     k_reduce_tree4;
+//   * everything else is the generic chain k_reduce_scaled<F, MODE> over Jacobian records -- a
+//     lane level with Jacobian inputs included (no shipped constant produces one; variant builds
+//     can).
 eIcicleError plan_levels(MsmPlan& p, int Wl) {
     constexpr int row_log = MBLS_ROW_SEG_LOG, row_log_g2 = MBLS_ROW_SEG_LOG_G2, seg0_log = MBLS_SEG0_LOG,
                   wave_log = MBLS_WSEG_LOG, lane_levels = MBLS_LANE_LEVELS;
@@ -245,16 +293,53 @@ eIcicleError plan_levels(MsmPlan& p, int Wl) {
         if (p.levels >= lanes_to || lane_chains < lmin) {
             const int rl = p.fq2 ? row_log_g2 : row_log;
             const uint32_t row_chains = ((m + (1u << rl) - 1) >> rl) * (uint32_t)Wl;
-            mode = row_chains >= wave_min_chains(p.fq2) ? MODE_ROW : MODE_WAVE;
+            mode = row_chains >= (p.fq2 ? MBLS_WAVE_MIN_G2 : MBLS_WAVE_MIN) ? MODE_ROW : MODE_WAVE;
             lg = mode == MODE_ROW ? rl : wave_log;
         }
+        const uint32_t mo = (m + (1u << lg) - 1) >> lg;
         p.seg_log[p.levels] = (uint8_t)lg;
         p.mode[p.levels] = (uint8_t)mode;
-        p.level_m[p.levels++] = m;
-        const uint32_t seg = p.seg(p.levels - 1);
-        uint32_t mo = (m + seg - 1) / seg;
+        p.off[p.levels] = p.levels == 0 ? 1 : 0;
+        p.level_m[p.levels] = m;
+        p.level_out[p.levels++] = mo;
         if (mo <= 1) break;
         m = mo;
+    }
+    // the launches and the record formats
+    const size_t jac = p.fq2 ? PointSize<Fq2>::JAC : PointSize<Fq>::JAC;
+    const size_t xyzz = p.fq2 ? xyzz_bytes<Fq2>() : xyzz_bytes<Fq>();
+    p.bucket_raw = p.mode[0] == MODE_LANE;
+    p.bucket_bytes = p.bucket_raw ? xyzz : jac;
+    p.level_bytes = jac;
+    p.launches = 0;
+    bool raw = p.bucket_raw;  // the next level's inputs are raw
+    for (int l = 0; l < p.levels;) {
+        const bool next = l + 1 < p.levels;
+        RedLaunch L{RED_CHAIN, (uint8_t)l, 1};
+        bool raw_out = false;
+        if (raw && !p.fq2) {
+            L.kernel = RED_R28X;
+            if (next && p.mode[l + 1] == MODE_ROW && p.seg_log[l + 1] == 3) {
+                L.kernel = RED_TREE8;  // level l's outputs stay in the lanes as raw XYZZ
+                L.nlevels = 2;
+                p.raw_out[l] = p.raw_in[l + 1] = 1;
+                p.launch_of[l + 1] = (uint8_t)p.launches;
+            }
+        } else if (raw) {
+            L.kernel = RED_R28PX;
+            raw_out = next && p.mode[l + 1] == MODE_LANE;
+        } else if (p.mode[l] == MODE_WAVE && p.seg_log[l] == 2 && p.off[l] == 0 &&
+                   p.level_out[l] * (uint32_t)Wl <= MBLS_TREE_MAX) {
+            L.kernel = RED_TREE4;
+        }
+        const int lo = l + L.nlevels - 1;  // the level whose outputs the launch writes
+        p.raw_in[l] = raw ? 1 : 0;
+        p.raw_out[lo] = raw_out ? 1 : 0;
+        if (raw_out) p.level_bytes = xyzz;
+        p.launch_of[l] = (uint8_t)p.launches;
+        p.launch[p.launches++] = L;
+        raw = raw_out;
+        l = lo + 1;
     }
     return MBLS_SUCCESS;
 }
@@ -306,7 +391,8 @@ MBLS_DEV void window_span(int j, int c, int Wg, int sF, int& pos, int& wid) {
 //    split) live in mbls_split.hpp with the GLV and psi splits, shared with scalar_mul.hip.
 
 // ------------------------------------------------------------------------------------
-// 1. digits: one thread per scalar
+// 1. digits, c > 16 (the atomic-rank sort: k_digits / k_digits_glv, the scan of section 2 and
+//    k_scatter of section 3): one thread per scalar
 // ------------------------------------------------------------------------------------
 template <bool MONT>
 __global__ __launch_bounds__(256) void k_digits(const uint8_t* __restrict__ scalars, uint32_t n, int c, int W, int Wg, int sF, uint32_t F,
@@ -595,12 +681,10 @@ eIcicleError launch_psi_table(const uint8_t* bases, uint8_t* phi, uint32_t n, hi
 }
 
 // ------------------------------------------------------------------------------------
-// 1c. tiled digits (c <= 16): workgroup (tile, window) histograms its tile's digits in LDS
-//     (local rank = LDS atomic return), then flushes the histogram with ONE coalesced
-//     returning global add per bucket (base of this tile in the bucket).  Random-address
-//     global atomics run ~17x below the coalesced rate on CDNA4 (MI355X_MICROARCH.md, global
-//     atomics: "64 lanes in 64 different rows"); this is what k_digits paid per digit.
-//     Digit sources: NW words per index (GLV halves: 4 words, bit 127 = sign; plain: 8 words).
+// 1c. digit sources of the partitioned sort (c <= 16, section 2b): the split kernels write NW
+//     words per index (GLV halves / psi quarters: 4 words, bit 127 = sign; plain: 8 words),
+//     which k_digits_part reads a tile of DT_TILE indices at a time.  c > 16 keeps k_digits /
+//     k_digits_glv above: global-atomic ranks, the three-kernel scan and k_scatter.
 // ------------------------------------------------------------------------------------
 static constexpr int DT_THREADS = 1024;
 #ifndef MBLS_DT_PER
@@ -678,104 +762,18 @@ __global__ void k_scalars_std(const uint8_t* __restrict__ scalars, uint32_t n, u
     store<FrCfg>(out + 32 * (size_t)i, from_mont(load<FrCfg>(scalars + 32 * (size_t)i)));
 }
 
-// signed digit of window w (carry chain from window 0), magnitude in v, sign in bit 31
-template <int NW>
-MBLS_DEV uint32_t digit_at(const uint32_t (&x)[NW], int w, int c, uint32_t B, int Wg, int sF) {
-    uint32_t carry = 0, v = 0;
-    for (int j = 0; j <= w; ++j) {
-        int bit, wid;
-        window_span(j, c, Wg, sF, bit, wid);
-        const int word = bit >> 5, sh = bit & 31;
-        uint32_t lo = 0, hi = 0;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) {
-            lo = (k == word) ? x[k] : lo;
-            hi = (k == word + 1) ? x[k] : hi;
-        }
-        v = ((uint32_t)((((uint64_t)hi << 32) | lo) >> sh) & ((1u << wid) - 1)) + carry;
-        carry = v > B ? 1u : 0u;
-    }
-    return carry ? (((1u << c) - v) | 0x80000000u) : v;
-}
-
-// GLV: indices [0, 2n) over the split halves, vals (idx << 1 | sign), key w*B + v - 1.
-// plain: indices [0, n) over scalars, vals ((i*F + w/Wg) << 1 | sign), key (w%Wg)*B + v - 1.
-template <bool GLV>
-__global__ __launch_bounds__(DT_THREADS) void k_digits_tiled(const uint32_t* __restrict__ src, uint32_t nidx, int c,
-                                                             int Wg, int sF, uint32_t F, uint32_t B,
-                                                             uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
-                                                             uint32_t* __restrict__ ranks, uint32_t* __restrict__ counts) {
-    __shared__ uint32_t hist[DT_MAX_B];
-    constexpr int NW = GLV ? 4 : 8;
-    const uint32_t tiles = (nidx + DT_TILE - 1) / DT_TILE;
-    const uint32_t tile = blockIdx.x % tiles;
-    const int w = (int)(blockIdx.x / tiles);
-    const uint32_t wl = GLV ? (uint32_t)w : (uint32_t)(w % Wg), f = GLV ? 0u : (uint32_t)(w / Wg);
-    for (uint32_t j = threadIdx.x; j < B; j += DT_THREADS) hist[j] = 0;
-    __syncthreads();
-    uint32_t dig[DT_PER], lr[DT_PER];
-#pragma unroll
-    for (int k = 0; k < DT_PER; ++k) {
-        const uint32_t idx = tile * DT_TILE + k * DT_THREADS + threadIdx.x;
-        dig[k] = 0;
-        lr[k] = 0;
-        if (idx < nidx) {
-            uint32_t x[NW];
-            const uint4* p = reinterpret_cast<const uint4*>(src) + (size_t)idx * (NW / 4);
-#pragma unroll
-            for (int q = 0; q < NW / 4; ++q) {
-                const uint4 u = p[q];
-                x[4 * q] = u.x;
-                x[4 * q + 1] = u.y;
-                x[4 * q + 2] = u.z;
-                x[4 * q + 3] = u.w;
-            }
-            uint32_t negh = 0;
-            if constexpr (GLV) {
-                negh = x[3] >> 31;
-                x[3] &= 0x7fffffffu;
-            } else {
-                reduce_scalar_words(x);  // standard scalars read in place (section 0)
-            }
-            const uint32_t d = digit_at<NW>(x, w, c, B, Wg, sF) ^ (negh << 31);
-            dig[k] = d;
-            if (d & 0x7fffffffu) lr[k] = atomicAdd(&hist[(d & 0x7fffffffu) - 1], 1u);
-        }
-    }
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < B; j += DT_THREADS) {
-        const uint32_t h = hist[j];
-        hist[j] = h ? atomicAdd(&counts[wl * B + j], h) : 0u;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < DT_PER; ++k) {
-        const uint32_t idx = tile * DT_TILE + k * DT_THREADS + threadIdx.x;
-        if (idx >= nidx) continue;
-        const size_t o = (size_t)w * nidx + idx;
-        const uint32_t v = dig[k] & 0x7fffffffu, sign = dig[k] >> 31;
-        if (v == 0) {
-            keys[o] = INVALID_KEY;
-            continue;
-        }
-        keys[o] = wl * B + v - 1;
-        vals[o] = ((GLV ? idx : idx * F + f) << 1) | sign;
-        ranks[o] = hist[v - 1] + lr[k];
-    }
-}
-
 // digit sources per scalar: GLV 2 x 16 B, psi 4 x 16 B, plain standard scalars 32 B
 size_t digits_src_bytes(uint32_t n, int split) { return (size_t)n * (split == 4 ? 64 : 32); }
 
-// the tiled digit kernels' sources: split halves / quarters (sign-magnitude uint4s) or
-// standard-form scalars; nidx = digit-source entries
+// k_digits_part's sources: split halves / quarters (sign-magnitude uint4s) or standard-form
+// scalars; nidx = digit-source entries
 __global__ void k_zero_list(ZeroList z) { z.run(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x); }
 
 // the MSM's first kernel also clears the words later kernels accumulate into (ZeroList): a
 // separate hipMemsetAsync is a fill kernel of its own, ~9-18 us on the critical path each
 static eIcicleError digit_sources(const uint8_t* scalars, bool mont, uint32_t n, const MsmPlan& P, uint8_t* dsrc,
                                   const ZeroList& z, hipStream_t st, const uint32_t*& src, uint32_t& nidx,
-                                  const uint8_t* bases = nullptr, uint8_t* phi = nullptr) {
+                                  const uint8_t* bases, uint8_t* phi) {
     dim3 g((n + 255) / 256);
     // digit-source (= point) index of stream j of scalar i: j n + i against the per-call image
     // table, i S + j against a prepared point-major table [P, phi P] / [P, psi P, psi^2 P, psi^3 P]
@@ -825,24 +823,8 @@ static eIcicleError digit_sources(const uint8_t* scalars, bool mont, uint32_t n,
 }
 
 eIcicleError launch_digits(const uint8_t* scalars, bool mont, uint32_t n, const MsmPlan& P, uint32_t* keys,
-                           uint32_t* vals, uint32_t* ranks, uint32_t* counts, uint8_t* dsrc, hipStream_t st) {
+                           uint32_t* vals, uint32_t* ranks, uint32_t* counts, hipStream_t st) {
     dim3 g((n + 255) / 256);
-    if (P.B <= DT_MAX_B) {
-        const uint32_t* src;
-        uint32_t nidx;
-        eIcicleError er = digit_sources(scalars, mont, n, P, dsrc, ZeroList{}, st, src, nidx);
-        if (er != MBLS_SUCCESS) return er;
-        const uint32_t tiles = (nidx + DT_TILE - 1) / DT_TILE;
-        dim3 gt(tiles * (uint32_t)P.W);
-        if (P.split > 1)  // GLV / psi sources share the sign-magnitude uint4 format
-            hipLaunchKernelGGL(k_digits_tiled<true>, gt, dim3(DT_THREADS), 0, st, src, nidx, P.c, P.Wg, P.sF, (uint32_t)P.F,
-                               P.B, keys, vals, ranks, counts);
-        else
-            hipLaunchKernelGGL(k_digits_tiled<false>, gt, dim3(DT_THREADS), 0, st, src, nidx, P.c, P.Wg, P.sF,
-                               (uint32_t)P.F, P.B, keys, vals, ranks, counts);
-        MBLS_TRY(hipGetLastError());
-        return MBLS_SUCCESS;
-    }
     if (P.split == 4) return MBLS_INVALID_ARGUMENT;  // make_plan keeps psi to c <= 16
     if (P.split == 2) {
         const SplitLayout lay = P.prepared ? SplitLayout{1u, 2u} : SplitLayout{n, 1u};
@@ -863,7 +845,8 @@ eIcicleError launch_digits(const uint8_t* scalars, bool mont, uint32_t n, const 
 }
 
 // ------------------------------------------------------------------------------------
-// 2. exclusive scan: three phases, 1024 elements per block, wave64 shuffles
+// 2. exclusive scan (the atomic-rank sort's bucket offsets): three phases, 1024 elements per
+//    block, wave64 shuffles
 // ------------------------------------------------------------------------------------
 // (wave_incl_scan: msm_core.hpp)
 
@@ -974,8 +957,8 @@ PartSortSizes part_sort_sizes(const MsmPlan& P) {
 
 // Signed digits in closed form: with C = sum (B - 1) 2^pos_w over the full-width windows w, the
 // bits e_w of s + C at window w's span (window_span) give d_w = e_w - (B - 1) in [1 - B, B] for a
-// full window -- the unique signed representation with that digit range, so exactly digit_at's
-// carry-chain digits, without its loop over the lower windows (O(w) per digit) -- and d_w = e_w
+// full window -- the unique signed representation with that digit range, so exactly k_digits'
+// carry-chain digits, without a loop over the lower windows (O(w) per digit) -- and d_w = e_w
 // for the narrower top window of a shift-table block (sF not a multiple of c), which never
 // carries in the chain.  The two representations differ only where a narrow window's digits and
 // carry add up to 2^wid (the chain's digit 2^wid, here 0 and one more in the next block); both
@@ -1778,7 +1761,7 @@ eIcicleError launch_order_scan(const uint32_t* binhist, uint32_t* binbase, uint3
 }
 
 // ------------------------------------------------------------------------------------
-// 3. scatter (counting sort)
+// 3. scatter of the atomic-rank sort (c > 16)
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_scatter(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                  const uint32_t* __restrict__ ranks, size_t total,

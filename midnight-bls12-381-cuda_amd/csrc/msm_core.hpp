@@ -23,11 +23,10 @@
 //                     inputs in segments of 2^s; each segment's chain walks R += V_t, S += R,
 //                     S += U_t and outputs U' = S and V' = 2^s R, so every level's outputs carry
 //                     weight 1 and the last level's output IS the window sum (no scalar
-//                     multiplications, no per-level tree sums, no window Horner).  Lane levels
-//                     over raw XYZZ records: k_reduce_scaled_r28x (G1) / _r28px (G2); row and
-//                     wave levels: k_reduce_scaled<F, MODE>, narrow ones k_reduce_tree4.  G1's lane
-//                     level 0 and row level 1 run as one launch, level 1 as a lane-arithmetic
-//                     tree over eight lanes per segment (k_reduce_tree8_r28x).
+//                     multiplications, no per-level tree sums, no window Horner).  Which kernel
+//                     runs which level, and the record formats between them, is plan data
+//                     (MsmPlan::launch, RedKernel; decided once by plan_levels, msm_common.hip):
+//                     msm_device launches it and msm_scratch sizes its buffers from it.
 //   7. k_final        fold over windows: sum_w 2^(c w) G_w; k_final_icicle adds ICICLE's
 //                     (x, y, 1) normalisation in the same launch.
 // Precompute factor F (bases table = F blocks of n bases, block f = 2^(c*Wg*f) * P) folds
@@ -93,6 +92,26 @@ struct SplitLayout {
     MBLS_DEV uint32_t at(uint32_t j, uint32_t i) const { return j * sj + i * si; }
 };
 
+// execution modes of the serial phases: one point chain per LANE (scalar arithmetic), per
+// 16-lane ROW (row-sliced), or per WAVE (row-sliced, independent products spread over rows)
+enum : int { MODE_LANE = 0, MODE_ROW = 1, MODE_WAVE = 2 };
+
+// The bucket reduction's schedule (section 6), decided by plan_levels (msm_common.hip) and only
+// read everywhere else: msm_device launches it, msm_scratch sizes its buffers, mbls_msm_reduce_plan
+// exports it.
+enum RedKernel : uint8_t {
+    RED_CHAIN = 0,  // k_reduce_scaled<F, MODE>: the generic chain over Jacobian records, in the level's mode
+    RED_TREE4 = 1,  // k_reduce_tree4<F>: a narrow wave level of 4-input segments
+    RED_R28X = 2,   // k_reduce_scaled_r28x (G1): lane level 0 over raw XYZZ buckets
+    RED_TREE8 = 3,  // k_reduce_tree8_r28x (G1): that level and the row level 1 behind it, one launch
+    RED_R28PX = 4,  // k_reduce_scaled_r28px (G2): a lane level over raw pair XYZZ records
+};
+struct RedLaunch {
+    uint8_t kernel;  // RedKernel
+    uint8_t level;   // its first level
+    uint8_t nlevels; // levels it covers (2: RED_TREE8)
+};
+
 struct MsmPlan {
     int c, W, Wg, F;
     int sF;                     // precomputed-table block shift in bits (0: F == 1), see window_span
@@ -107,9 +126,18 @@ struct MsmPlan {
     size_t contributions;
     int levels;                 // bucket-reduction levels
     uint32_t level_m[MAX_LEVELS];  // inputs per window at each level
+    uint32_t level_out[MAX_LEVELS];  // outputs per window (segments) at each level
     uint8_t seg_log[MAX_LEVELS];   // log2 segment length per level
     uint8_t mode[MAX_LEVELS];      // MODE_LANE / MODE_ROW / MODE_WAVE per level
-    uint32_t seg(int l) const { return 1u << seg_log[l]; }
+    uint8_t off[MAX_LEVELS];       // weight of a level's input t is t + off (1 at level 0: bucket t holds digit t + 1)
+    uint8_t raw_in[MAX_LEVELS];    // the level reads raw XYZZ limbs (else Jacobian words)
+    uint8_t raw_out[MAX_LEVELS];   // the level writes raw XYZZ limbs
+    uint8_t launch_of[MAX_LEVELS]; // the launch a level belongs to
+    int launches;
+    RedLaunch launch[MAX_LEVELS];
+    bool bucket_raw;               // the bucket sums are raw XYZZ records (= raw_in[0])
+    size_t bucket_bytes;           // a bucket record's bytes
+    size_t level_bytes;            // a level output record's bytes (raw when any level writes raw)
 };
 
 // endo: the split the group offers (1 none, 2 G1 GLV, 4 G2 psi); make_plan decides whether to use it
@@ -119,8 +147,9 @@ eIcicleError plan_levels(MsmPlan& p, int Wl);
 int precompute_shift(int F);
 
 // ---- non-templated launchers (msm_common.hip) ----------------------------------------
+// c > 16: digits as (key, value) pairs with global-atomic ranks (k_digits / k_digits_glv)
 eIcicleError launch_digits(const uint8_t* scalars, bool mont, uint32_t n, const MsmPlan& P, uint32_t* keys,
-                           uint32_t* vals, uint32_t* ranks, uint32_t* counts, uint8_t* dsrc, hipStream_t st);
+                           uint32_t* vals, uint32_t* ranks, uint32_t* counts, hipStream_t st);
 size_t digits_src_bytes(uint32_t n, int split);
 eIcicleError scan_exclusive(const uint32_t* in, uint32_t* out, uint32_t m, uint32_t* tmp, hipStream_t st);
 eIcicleError launch_chunk_counts(const uint32_t* counts, const uint32_t* offsets, uint32_t* nchunks, uint32_t m,
@@ -494,10 +523,7 @@ MBLS_DEV uint32_t row_id() { return (blockIdx.x * blockDim.x + threadIdx.x) >> 4
 // segments); the later, narrower levels run one segment per ROW (row-sliced arithmetic).
 // Single jac_add call site: the loop alternates the R and S updates.
 // ------------------------------------------------------------------------------------
-// execution modes of the serial phases: one point chain per LANE (scalar arithmetic), per
-// 16-lane ROW (row-sliced), or per WAVE (row-sliced, independent products spread over rows)
-enum : int { MODE_LANE = 0, MODE_ROW = 1, MODE_WAVE = 2 };
-
+// the execution modes (MODE_LANE / MODE_ROW / MODE_WAVE, above MsmPlan) as point arithmetic
 template <class F, int MODE>
 struct RedIO;
 template <class F>
@@ -986,7 +1012,7 @@ __global__ __launch_bounds__(256) void k_reduce_scaled(const uint8_t* __restrict
     IO::st(Uout, tid, S);
 }
 
-// G1's lane-mode level 0 over raw XYZZ buckets (buckets_xyzz, no U) in radix 2^28: the chain of
+// G1's lane-mode level 0 over raw XYZZ buckets (MsmPlan::bucket_raw, no U) in radix 2^28: the chain of
 // k_reduce_scaled with add-2008-s (r28::xadd, 12M + 2S) for its two additions per step, the
 // outputs converted once.  Bucket t - 1 is loaded before bucket t is added.
 // One lane's chain over buckets [k0, k1) of the window at record `base`: S = sum (t - k0 + off) V_t
@@ -1473,55 +1499,22 @@ __global__ __launch_bounds__(128) void k_precompute(const uint8_t* in, uint8_t* 
 // ------------------------------------------------------------------------------------
 // the scratch blocks of one MSM, in arena order; msm_scratch below is their one description
 struct MsmScratch {
-    uint32_t *keys, *vals, *ranks;  // tiled sort (zero bytes with the partitioned sort)
+    uint32_t *keys, *vals, *ranks;  // atomic-rank sort, c > 16 (zero bytes with the partitioned sort)
     uint8_t* dsrc;
     uint32_t *sorted, *counts, *offsets, *nchunks, *chunk_off, *tmp, *owner, *first;
     uint8_t *partials, *buckets, *levelT, *levelR, *windows;
     uint8_t* phi;                                  // the per-call image table, or null
-    uint32_t *ent, *seg_off, *seg_cnt, *part_tot;  // partitioned sort (zero bytes with the tiled sort)
+    uint32_t *ent, *seg_off, *seg_cnt, *part_tot;  // partitioned sort (zero bytes with the atomic-rank sort)
     PartHelp ph;
     uint32_t *binhist, *binbase, *perm;  // k_bucket_order: bin histograms, their scan, bucket permutation
     HeavyTab H;
 };
 
-// reduction levels with fewer segments than this run one segment per wave (-DMBLS_WAVE_MIN tunes;
-// G2: MBLS_WAVE_MIN_G2).  An Fq2 row-sliced addition is three row products per Fq2 product in
-// series, so G2 switches to the wave layout (the three spread over rows) at more segments
-// (8192, with G2 row segments of 8: msm_common.hip plan_levels; 4096 measured 1.75 ms of G2
-// reduction at 2^20, 8192 and 16384 1.64 ms).
 // Tuning knobs in this file are compile-time macros for tools/ variant builds (never run-time
 // environment reads: a prover's environment must not select untested kernels).
-#ifndef MBLS_WAVE_MIN
-#define MBLS_WAVE_MIN 2048u
-#endif
-#ifndef MBLS_WAVE_MIN_G2
-#define MBLS_WAVE_MIN_G2 8192u
-#endif
-inline uint32_t wave_min_chains(bool fq2 = false) { return fq2 ? MBLS_WAVE_MIN_G2 : MBLS_WAVE_MIN; }
 
 // the endomorphism images of the bases are built per call (msm_device's `phi` block)
 inline bool msm_image_table(const MsmPlan& P) { return P.split > 1 && !P.prepared; }
-// raw XYZZ buckets for this plan (level 0 in lanes)
-template <class F>
-inline bool buckets_xyzz(const MsmPlan& P) {
-    return P.levels > 0 && P.mode[0] == MODE_LANE;
-}
-// a level output record's bytes: raw pair XYZZ (448) when G2 chains lane levels (they take raw
-// records from the level before), else Jacobian
-// G1's row level 1 of 8-input segments behind a lane level 0 runs as the lane-arithmetic tree
-// (k_reduce_tree8_r28x).  Every other row level keeps k_reduce_scaled<F, MODE_ROW>: a row level 0
-// (off = 1, the c = 13 plans), other segment lengths, G2.
-template <class F>
-inline bool tree8_level1(const MsmPlan& P) {
-    return std::is_same<F, Fq>::value && buckets_xyzz<F>(P) && P.levels > 1 &&
-           P.mode[1] == MODE_ROW && P.seg_log[1] == 3;
-}
-template <class F>
-inline size_t level_bytes(const MsmPlan& P) {
-    return (std::is_same<F, Fq2>::value && buckets_xyzz<F>(P) && P.levels > 1 && P.mode[1] == MODE_LANE)
-               ? xyzz_bytes<F>()
-               : PointSize<F>::JAC;
-}
 // The one description of an MSM's scratch region: every block in arena order, its bytes and the
 // pointer it becomes.  With `base` it carves the region into S; without (the counting pass) S's
 // pointers are null.  Either way it returns the region's bytes (a sum of 256-byte multiples).
@@ -1554,11 +1547,10 @@ inline size_t msm_scratch(const MsmPlan& P, uint8_t* base, MsmScratch& S) {
     take(S.owner, 4 * (size_t)max_chunks);
     take(S.first, 4 * (NC / P.chunk + 2));
     take(S.partials, (size_t)max_chunks * xyzz_bytes<F>());
-    take(S.buckets, (size_t)P.TB * (buckets_xyzz<F>(P) ? xyzz_bytes<F>() : jac));
-    // V / U ping-pong halves sized for the widest level's outputs (k_reduce_scaled)
-    const size_t mo0 = P.levels ? (P.level_m[0] + P.seg(0) - 1) / P.seg(0) : 1;
-    take(S.levelT, 2 * mo0 * P.Wg * level_bytes<F>(P));
-    take(S.levelR, 2 * mo0 * P.Wg * level_bytes<F>(P));
+    take(S.buckets, (size_t)P.TB * P.bucket_bytes);
+    // V / U ping-pong halves sized for the widest level's outputs (level 0's; msm_device's `half`)
+    take(S.levelT, 2 * (size_t)P.level_out[0] * P.Wg * P.level_bytes);
+    take(S.levelR, 2 * (size_t)P.level_out[0] * P.Wg * P.level_bytes);
     take(S.windows, (size_t)P.Wg * jac);
     // the per-call image table; with bstride > 1 also the compact copy of the points (2n rows)
     S.phi = nullptr;
@@ -1641,31 +1633,24 @@ inline uint32_t accumulate_chunk(const MsmPlan& P) {
 #endif
 inline int batch_pipe() { return MBLS_BATCH_PIPE; }
 
-// wave-layout levels of 4-input segments with at most this many segments run as trees of 4
-// waves (k_reduce_tree4; -DMBLS_TREE_MAX tunes, 0 disables)
-#ifndef MBLS_TREE_MAX
-#define MBLS_TREE_MAX 512u
-#endif
-inline uint32_t tree_max_chains() { return MBLS_TREE_MAX; }
-
-// one reduction level over Wl windows (weights t + off; off = 1 at level 0: bucket t holds digit t + 1)
+// RED_CHAIN: one level over Wl windows as the generic chain, in the level's mode.  A lane level
+// lands here only with Jacobian inputs, which no shipped plan has (plan_levels).
 template <class F>
-inline void launch_reduce_scaled(int mode, const uint8_t* V, const uint8_t* U, uint32_t m_in, uint32_t seg_log, int Wl,
-                                 int off, uint8_t* Vo, uint8_t* Uo, uint32_t chains, hipStream_t s) {
-    constexpr uint32_t LN = LaneOf<F>::LANES;
-    if (mode == MODE_WAVE && seg_log == 2 && off == 0 && chains <= tree_max_chains()) {
-        hipLaunchKernelGGL(k_reduce_tree4<F>, dim3(chains), dim3(256), 0, s, V, U, m_in, Vo, Uo);
-        return;
-    }
-    if (mode == MODE_LANE)  // the one fallback: a shipped plan's lane levels all read raw XYZZ records (msm_device)
-        hipLaunchKernelGGL((k_reduce_scaled<F, MODE_LANE>), dim3((chains * LN + 255) / 256), dim3(256), 0, s, V, U, m_in,
-                           seg_log, Wl, off, Vo, Uo);
-    else if (mode == MODE_ROW)
+inline void launch_reduce_chain(int mode, const uint8_t* V, const uint8_t* U, uint32_t m_in, uint32_t seg_log, int Wl,
+                                int off, uint8_t* Vo, uint8_t* Uo, uint32_t chains, hipStream_t s) {
+    switch (mode) {
+    case MODE_LANE:
+        hipLaunchKernelGGL((k_reduce_scaled<F, MODE_LANE>), dim3((chains * LaneOf<F>::LANES + 255) / 256), dim3(256), 0, s,
+                           V, U, m_in, seg_log, Wl, off, Vo, Uo);
+        break;
+    case MODE_ROW:
         hipLaunchKernelGGL((k_reduce_scaled<F, MODE_ROW>), dim3((chains * 16 + 255) / 256), dim3(256), 0, s, V, U, m_in,
                            seg_log, Wl, off, Vo, Uo);
-    else
+        break;
+    default:
         hipLaunchKernelGGL((k_reduce_scaled<F, MODE_WAVE>), dim3((chains * 64 + 255) / 256), dim3(256), 0, s, V, U, m_in,
                            seg_log, Wl, off, Vo, Uo);
+    }
 }
 
 // Batch tail pipeline (msm_call, batch_size > 1): member b's reduction levels and final fold --
@@ -1712,7 +1697,6 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
     }
     const uint32_t TB = P.TB;
     const size_t NC = P.contributions;
-    const bool xb = buckets_xyzz<F>(P);
     const bool img_table = msm_image_table(P), psort = partition_sort(P);
     MsmScratch S;
     uint8_t* region = static_cast<uint8_t*>(arena.take(msm_scratch_bytes<F>(P)));
@@ -1732,7 +1716,7 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
     hipStream_t side = ctx.sides[0];
     hipEvent_t* ev = ctx.events.data();
     // with the partitioned sort the endomorphism table is written by the split kernel
-    // (k_glv_prep / k_psi_prep); the tiled sort (c > 16) builds it on the side stream
+    // (k_glv_prep / k_psi_prep); the atomic-rank sort (c > 16) builds it on the side stream
     const bool fused_table = img_table && psort;
     if (img_table && !fused_table) {  // endomorphism images of the bases: phi(P) (G1) or psi^1..3(P) (G2)
         ctx.forked = true;
@@ -1754,7 +1738,7 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
                                     fused_cc ? S.binhist : nullptr, fused_cc ? order_words(TB) : 0u);
         } else {
             MBLS_TRY(hipMemsetAsync(S.counts, 0, (size_t)TB * 4, st));
-            er = launch_digits(scalars, scalars_mont, n, P, S.keys, S.vals, S.ranks, S.counts, S.dsrc, st);
+            er = launch_digits(scalars, scalars_mont, n, P, S.keys, S.vals, S.ranks, S.counts, st);
         }
         if (er != MBLS_SUCCESS) return er;
     }
@@ -1819,7 +1803,7 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
         const uint32_t light_blocks = (TB * LN + 255) / 256;
         if (pipe && pipe->reuse) MBLS_TRY(hipStreamWaitEvent(st, pipe->reuse, 0));
         hipLaunchKernelGGL(k_bucket_small<F>, dim3(light_blocks + HEAVY_BLOCKS), dim3(256), 0, st, S.chunk_off, S.perm,
-                           S.binbase, order_words(TB), S.partials, S.buckets, light_blocks, S.H, xb ? 1 : 0);
+                           S.binbase, order_words(TB), S.partials, S.buckets, light_blocks, S.H, P.bucket_raw ? 1 : 0);
     }
     if (pipe) {  // the tail moves to the side stream
         MBLS_TRY(hipEventRecord(pipe->bucket_done, st));
@@ -1828,43 +1812,49 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
     }
     {
         ProfScope ps_red("msm.reduce", st);  // the levels only (k_final has its own scope)
-        // scaled running-sum levels (k_reduce_scaled): V / U ping-pong in levelR / levelT, the
-        // last level writes the window sums straight into `windows`
-        const size_t half = ((P.level_m[0] + P.seg(0) - 1) / P.seg(0)) * (size_t)P.Wg * level_bytes<F>(P);
+        // the plan's launches in order (plan_levels): V / U ping-pong in levelR / levelT by the
+        // parity of a launch's last level, whose outputs it writes; the plan's last level writes
+        // the window sums straight into `windows`
+        const size_t half = (size_t)P.level_out[0] * (size_t)P.Wg * P.level_bytes;
         uint8_t* vb[2] = {S.levelR, S.levelR + half};
         uint8_t* ub[2] = {S.levelT, S.levelT + half};
         const uint8_t* V = S.buckets;
         const uint8_t* U = nullptr;
-        bool raw_in = xb;  // level l's inputs are raw XYZZ records
-        for (int l = 0; l < P.levels; ++l) {
-            const uint32_t m_in = P.level_m[l];
-            const uint32_t m_out = (m_in + P.seg(l) - 1) / P.seg(l);
-            const bool last = l == P.levels - 1;
-            uint8_t* Vo = last ? nullptr : vb[l & 1];
-            uint8_t* Uo = last ? S.windows : ub[l & 1];
-            const uint32_t chains = m_out * (uint32_t)P.Wg;
-            if (!raw_in) {
-                launch_reduce_scaled<F>(P.mode[l], V, U, m_in, P.seg_log[l], P.Wg, l == 0 ? 1 : 0, Vo, Uo, chains, st);
-            } else if constexpr (std::is_same<F, Fq>::value) {  // lane level 0
-                if (tree8_level1<F>(P)) {
-                    // levels 0 and 1 in one launch: the lane keeps its level-0 outputs for the tree
-                    const uint32_t m1 = P.level_m[1], mo1 = (m1 + 7) / 8;
-                    const bool last1 = P.levels == 2;
-                    Vo = last1 ? nullptr : vb[1];
-                    Uo = last1 ? S.windows : ub[1];
-                    hipLaunchKernelGGL((k_reduce_tree8_r28x<F>), dim3((8 * mo1 * (uint32_t)P.Wg + 255) / 256), dim3(256),
-                                       0, st, V, m_in, P.seg_log[0], m1, P.Wg, Vo, Uo);
-                    ++l;
-                } else {
+        for (int k = 0; k < P.launches; ++k) {
+            const int l = P.launch[k].level, lo = l + P.launch[k].nlevels - 1;
+            const bool last = lo == P.levels - 1;
+            uint8_t* Vo = last ? nullptr : vb[lo & 1];
+            uint8_t* Uo = last ? S.windows : ub[lo & 1];
+            const uint32_t m_in = P.level_m[l], seg_log = P.seg_log[l];
+            const uint32_t chains = P.level_out[lo] * (uint32_t)P.Wg;
+            const int off = P.off[l];
+            switch (P.launch[k].kernel) {
+            case RED_TREE4:
+                hipLaunchKernelGGL(k_reduce_tree4<F>, dim3(chains), dim3(256), 0, st, V, U, m_in, Vo, Uo);
+                break;
+            case RED_CHAIN:
+                launch_reduce_chain<F>(P.mode[l], V, U, m_in, seg_log, P.Wg, off, Vo, Uo, chains, st);
+                break;
+            case RED_TREE8:  // the lane keeps its level-0 outputs for the tree: eight lanes per level-1 segment
+                if constexpr (!std::is_same<F, Fq>::value) return MBLS_INVALID_ARGUMENT;
+                else
+                    hipLaunchKernelGGL((k_reduce_tree8_r28x<F>), dim3((8 * chains + 255) / 256), dim3(256), 0, st, V, m_in,
+                                       seg_log, P.level_m[lo], P.Wg, Vo, Uo);
+                break;
+            case RED_R28X:
+                if constexpr (!std::is_same<F, Fq>::value) return MBLS_INVALID_ARGUMENT;
+                else
                     hipLaunchKernelGGL((k_reduce_scaled_r28x<F>), dim3((chains + 255) / 256), dim3(256), 0, st, V, m_in,
-                                       P.seg_log[0], P.Wg, 1, Vo, Uo);
-                }
-                raw_in = false;
-            } else {  // G2: lane level 0, or the lane levels after it
-                const bool raw_out = !last && P.mode[l + 1] == MODE_LANE;
-                hipLaunchKernelGGL((k_reduce_scaled_r28px<F>), dim3((2 * chains + 255) / 256), dim3(256), 0, st, V, U,
-                                   m_in, P.seg_log[l], P.Wg, l == 0 ? 1 : 0, Vo, Uo, raw_out ? 1 : 0);
-                raw_in = raw_out;
+                                       seg_log, P.Wg, off, Vo, Uo);
+                break;
+            case RED_R28PX:
+                if constexpr (!std::is_same<F, Fq2>::value) return MBLS_INVALID_ARGUMENT;
+                else
+                    hipLaunchKernelGGL((k_reduce_scaled_r28px<F>), dim3((2 * chains + 255) / 256), dim3(256), 0, st, V, U,
+                                       m_in, seg_log, P.Wg, off, Vo, Uo, (int)P.raw_out[l]);
+                break;
+            default:
+                return MBLS_INVALID_ARGUMENT;
             }
             V = Vo;
             U = Uo;

@@ -1,5 +1,5 @@
 """Host-only model of the MSM's bucket reduction and window fold (csrc/msm_common.hip
-plan_levels, csrc/msm_core.hpp msm_device / launch_reduce_scaled / k_reduce_scaled* /
+plan_levels, csrc/msm_core.hpp msm_device / k_reduce_scaled* /
 k_reduce_tree4 / final_fold), over points written as integers mod r: the multiple of one fixed
 base point, 0 the identity.
 
@@ -27,7 +27,7 @@ from helpers import pyref
 
 R = pyref.R
 
-# ---- plan (msm_common.hip plan_levels; msm_core.hpp wave_min_chains / tree_max_chains) ------------
+# ---- plan (msm_common.hip plan_levels and its macros) ---------------------------------------------
 SEG0_LOG = 2          # level 0, one segment per lane
 SEGL_LOG_G2 = 1       # G2 lane levels after level 0
 ROW_SEG_LOG = 3       # G1 and G2

@@ -104,6 +104,24 @@ def plan(group="g1", c=16, bitsize=128):
     return pl
 
 
+def library_levels(sched):
+    """(kind, seg_log, m_in) per level of the library's own schedule (bls12_381_amd.msm_reduce_plan),
+    its (kernel, mode, level > 0) written in this model's kind names -- the form of plan()["levels"].
+    A lane level on the generic chain has no kind here ("laneJ": no shipped plan has one)."""
+    chain = {"lane": ("laneJ", "laneJ"), "row": ("row1", "rowU"), "wave": ("wave", "wave")}
+    out = []
+    for lvl, lv in enumerate(sched["levels"]):
+        kind = {"chain": chain[lv["mode"]], "tree4": ("tree4", "tree4"), "r28x": ("r28x", None),
+                "tree8": ("r28x", "tree8"), "r28px": ("r28px", "r28pxU")}[lv["kernel"]][min(lvl, 1)]
+        out.append((kind, lv["seg_log"], lv["m_in"]))
+    return out
+
+
+def model_levels(pl):
+    """plan()["levels"] in library_levels' form"""
+    return [(lv["kind"], lv["seg_log"], lv["m_in"]) for lv in pl["levels"]]
+
+
 def _segment(kind):
     return tree8 if kind == "tree8" else M._SEGMENT[kind]
 

@@ -60,6 +60,7 @@ import pytest
 
 import helpers as H
 import msm_reduce_model as M
+import reduce_tree_model as T
 from helpers import pyref as pr
 
 PKG = os.path.join(H.ROOT, "midnight-bls12-381-cuda_amd")
@@ -160,6 +161,10 @@ def test_model_plan_matches_library(lib_host, key):
         assert (p["split"], p["c"], p["W"], p["Wg"], p["F"]) == (1, c, pl["W"], pl["Wg"], 1), (n, p)
         assert p["buckets"] == pl["Wg"] * pl["B"]
         assert p["levels"] == len(pl["levels"]), (n, p)
+        # the kernels msm_device launches, from the library itself (level 1 of ("g1", 16, 128) is
+        # the tree since reduce_tree_model; this module's tables keep the chain's census there)
+        assert T.library_levels(lib_host.msm_reduce_plan(group, n, c=c, bitsize=bits)) == \
+            T.model_levels(T.plan(*key)), (n, p)
     assert [lv["kind"] for lv in pl["levels"]] == EXPECTED_KINDS[key]
     # the shapes the designs lean on: a short last tree segment, a row level at off = 1, lane
     # levels with U and 2-input segments

@@ -436,10 +436,10 @@ def test_msm_window_sizes(amd, gh):
         assert gh.decode_icicle("g2", r[0]) == expect2, c
 
 
-def test_msm_g1_unsplit_tiled_sort(amd, gh):
-    """G1 on the unsplit tiled-sort path (keys / vals / ranks + scatter, c > 16 without the GLV
-    split): plain bases reach it only through a narrow bitsize, so otherwise only G2 (c = 17, 18)
-    carves those scratch blocks.  Element-exact against pyref."""
+def test_msm_g1_unsplit_atomic_rank_sort(amd, gh):
+    """G1 on the unsplit atomic-rank sort (k_digits: keys / vals / ranks, scan + k_scatter; c > 16
+    without the GLV split): plain bases reach it only through a narrow bitsize, so otherwise only
+    G2 (c = 17, 18) carves those scratch blocks.  Element-exact against pyref."""
     plan = amd.msm_plan("g1", 300, bitsize=128, c=18)
     assert plan["split"] == 1 and plan["c"] == 18
     g = H.load_golden("msm_g1.json")

@@ -8,6 +8,10 @@ and the parity cases of the issue; everything is bit-exact against the oracle, n
 
 The reduction plan depends on c and the window count, not on n, so every case here runs the tree:
 c = 16 gives level 0 in lanes (8192 segments of 4 per window) and level 1 in 1024 segments of 8."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -16,6 +20,8 @@ import msm_reduce_model as M
 import reduce_tree_model as T
 from helpers import pyref as pr
 
+PKG = os.path.join(H.ROOT, "midnight-bls12-381-cuda_amd")
+LIB = os.path.join(PKG, "lib", "libbls12_381_mi355x.so")
 PLAN = T.plan(*T.KEY)
 TABLES = T.tables(PLAN)
 
@@ -43,9 +49,24 @@ MULT = Multiples()
 
 
 # ----------------------------------------------------------------------------- host: the model
-def test_plan_has_the_tree_level():
+@pytest.fixture(scope="module")
+def lib_host():
+    """the binding for host-only calls (msm_plan, msm_reduce_plan)"""
+    if not os.path.exists(LIB):
+        subprocess.check_call(["make", "-C", PKG, "-j8", "-s"])
+    sys.path.insert(0, PKG)
+    import bls12_381_amd
+    return bls12_381_amd
+
+
+def test_plan_has_the_tree_level(lib_host):
     lv = PLAN["levels"]
     assert [x["kind"] for x in lv] == ["r28x", "tree8", "wave", "wave", "tree4", "tree4", "tree4"]
+    # and these are the kernels the library launches for the unsplit plan, at every size used here
+    for n in (1, 64, 1 << 16, *(len(t.entries()) for t in TABLES)):
+        sched = lib_host.msm_reduce_plan("g1", n, c=T.KEY[1], bitsize=T.KEY[2])
+        assert T.library_levels(sched) == T.model_levels(PLAN), n
+        assert [x["launch"] for x in sched["levels"]] == [0, 0, 1, 2, 3, 4, 5]
     assert (lv[1]["m_in"], lv[1]["m_out"], lv[1]["seg_log"], lv[1]["off"], lv[1]["span"]) == (8192, 1024, 3, 0, 4)
     assert PLAN["Wg"] == 9
     # the level count is msm_reduce_model's (the library's: test_gpu_msm_exceptional pins it); the

@@ -1,8 +1,10 @@
 """CPU-only checks of the MSM schedule the library picks (make_plan through the host-only
 mbls_msm_plan diagnostics export; no device work): the split plans and their windows, prepared
 tables, and which precompute factors run the shift plan or the split plan on slot 0 of the table
-("Shift tables: which plan" and "Window sizes below 2^20").  The results of
-every plan are checked against the oracle by tests/test_gpu_prepared.py on the GPU."""
+("Shift tables: which plan" and "Window sizes below 2^20"), and the bucket
+reduction's kernel schedule (plan_levels through mbls_msm_reduce_plan) against the host model of
+tests/reduce_tree_model.py over every plan a caller can reach.  The results of every plan are
+checked against the oracle by tests/test_gpu_prepared.py on the GPU."""
 import os
 import subprocess
 import sys
@@ -97,3 +99,86 @@ def test_plan_argument_errors(amd):
         amd.msm_plan("g1", 1 << 10, c=21)
     with pytest.raises(amd.IcicleError):
         amd.msm_plan("g1", 1 << 10, bitsize=257)
+
+
+# ---- the bucket reduction's kernel schedule (plan_levels through mbls_msm_reduce_plan) -----------
+GRID_C = range(2, 21)
+GRID_BITS = (1, 32, 64, 127, 128, 129, 192, 193, 255)
+GRID_F = (1, 2, 4, 8, 16)
+GRID_N = (1, 1 << 12, 1 << 20)
+_MODEL = {}
+
+
+def _grid(amd, group, c):
+    for bits in GRID_BITS:
+        for F in GRID_F:
+            for n in GRID_N:
+                cfg = dict(c=c, bitsize=bits, precompute_factor=F)
+                yield (n, cfg), amd.msm_plan(group, n, **cfg), amd.msm_reduce_plan(group, n, **cfg)
+
+
+def _model(group, c, Wg):
+    import reduce_tree_model as T
+    if (group, c, Wg) not in _MODEL:
+        _MODEL[(group, c, Wg)] = T.model_levels(T.plan(group, c, c * Wg - 1))
+    return _MODEL[(group, c, Wg)]
+
+
+@pytest.mark.parametrize("c", GRID_C)
+@pytest.mark.parametrize("group", ["g1", "g2"])
+def test_reduce_schedule_equals_the_model(amd, group, c):
+    """per level the kernel's kind, the segment log and the inputs per window the library launches
+    are the ones tests/reduce_tree_model.py plans for the library's own (c, Wg): every caller's c,
+    bit sizes around the split thresholds, every kind of table, three sizes"""
+    import reduce_tree_model as T
+    for case, p, sched in _grid(amd, group, c):
+        assert p["levels"] == len(sched["levels"]), (case, p)
+        assert T.library_levels(sched) == _model(group, p["c"], p["Wg"]), (case, p)
+
+
+@pytest.mark.parametrize("c", GRID_C)
+@pytest.mark.parametrize("group", ["g1", "g2"])
+def test_reduce_schedule_structure(amd, group, c):
+    jac, xyzz = (144, 224) if group == "g1" else (288, 448)
+    for case, p, sched in _grid(amd, group, c):
+        lv = sched["levels"]
+        outs = [(x["m_in"] + (1 << x["seg_log"]) - 1) >> x["seg_log"] for x in lv]
+        assert lv[0]["m_in"] == 1 << (p["c"] - 1) and outs[-1] == 1, (case, lv)
+        for a, o, b in zip(lv, outs, lv[1:]):
+            assert b["m_in"] == o and b["raw_in"] == a["raw_out"], (case, lv)
+        for x in lv:
+            assert x["raw_in"] == (x["kernel"] in ("r28x", "tree8", "r28px")), (case, lv)
+            assert not x["raw_out"] or x["kernel"] in ("tree8", "r28px"), (case, lv)
+        assert not lv[-1]["raw_out"], (case, lv)
+        # launches: one level each, in order, but the tree: exactly levels 0 and 1 of a G1 plan
+        tree = [l for l, x in enumerate(lv) if x["kernel"] == "tree8"]
+        assert tree in ([], [0, 1]) and (not tree or group == "g1"), (case, lv)
+        assert [x["launch"] for x in lv] == [max(l - 1, 0) if tree else l for l in range(len(lv))], (case, lv)
+        assert all(x["kernel"] != "r28x" or (l == 0 and group == "g1") for l, x in enumerate(lv)), (case, lv)
+        assert all(x["kernel"] != "r28px" or (x["mode"] == "lane" and group == "g2") for x in lv), (case, lv)
+        assert sched["bucket_raw"] == lv[0]["raw_in"], (case, sched)
+        stored_raw = any(x["raw_out"] and x["kernel"] != "tree8" for x in lv)  # the tree's stay in the lanes
+        assert sched["level_bytes"] == (xyzz if stored_raw else jac), (case, sched)
+
+
+def test_reduce_schedule_grid_reaches_every_kind(amd):
+    import reduce_tree_model as T
+    seen = set()
+    for group in ("g1", "g2"):
+        for c in GRID_C:
+            for _, _, sched in _grid(amd, group, c):
+                seen |= {k for k, _, _ in T.library_levels(sched)}
+    assert seen == {"r28x", "tree8", "r28px", "r28pxU", "row1", "rowU", "wave", "tree4"}
+
+
+def test_reduce_plan_argument_errors(amd):
+    import ctypes
+    with pytest.raises(amd.IcicleError):
+        amd.msm_reduce_plan("g1", 1 << 10, c=21)
+    with pytest.raises(amd.IcicleError):
+        amd.msm_reduce_plan("g1", 1 << 10, bitsize=257)
+    cfg, out, cnt = amd.msm_config(), (ctypes.c_int32 * 4)(), ctypes.c_int32(0)
+    assert amd.lib().mbls_msm_reduce_plan(1, 1 << 20, ctypes.byref(cfg), out, 4, ctypes.byref(cnt)) == 11
+    assert cnt.value == 2 + 7 * amd.msm_plan("g1", 1 << 20)["levels"] and list(out) == [0] * 4
+    assert amd.lib().mbls_msm_reduce_plan(3, 1 << 20, ctypes.byref(cfg), out, 4, ctypes.byref(cnt)) == 11
+    assert amd.lib().mbls_msm_reduce_plan(1, 1 << 20, None, out, 4, ctypes.byref(cnt)) == 3
