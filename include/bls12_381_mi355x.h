@@ -260,6 +260,64 @@ eIcicleError mbls_fr_poly_divide_linear(const mbls_fr_t* coeffs, size_t size, co
 eIcicleError mbls_fr_scan_geometry(size_t size, int32_t* out);
 
 /* ------------------------------------------------------------------------------------ */
+/* Fr expression evaluator: one caller-supplied straight-line stack program run once per row over
+ * a set of columns read at rotated rows -- the permutation numerators and denominators that feed
+ * mbls_fr_prefix_product, the theta-compression of lookup columns, the gate / permutation / lookup
+ * folds of the quotient on the extended coset, linear combinations of polynomials.  One launch,
+ * one read of every column an op names, one write per output; the intermediates stay on chip.  (No
+ * reference counterpart: the reference composes these on the CPU.)
+ *   elements: Montgomery and canonical (< r), in and out; every output element is canonical.
+ *   rows: size in 1..2^26, any value, not only a power of two.  COLUMN reads row
+ *     (i + b * rot_stride) mod size: rot_stride is 1 on the base domain and 2^(extended_k - k) on
+ *     the extended one.  Any b and any rot_stride in 1..2^26 are legal: the host reduces
+ *     b * rot_stride modulo size (in 64-bit arithmetic, which holds every such product) and the
+ *     kernel only sees an offset in [0, size).
+ *   program: `program`, the `columns` pointer table and the counts are host memory, always.  The
+ *     columns themselves are placed by config->is_a_on_device (all alike), `constants` by
+ *     is_b_on_device, `output` (n_outputs * size elements, member-major: output k at k * size) by
+ *     is_result_on_device.  Host buffers are staged through the leased scratch context, which also
+ *     holds the resolved program (no allocation per call once it is large enough); a host output
+ *     makes the call synchronous, otherwise it synchronises unless is_async.  batch_size and
+ *     columns_batch are not read.
+ *   limits: n_ops in 1..4096, n_columns in 1..1024, n_constants in 0..1024, n_outputs in 1..8,
+ *     stack depth at most 8.
+ *   errors, all before any device work (the host simulates the stack): INVALID_POINTER for a null
+ *     columns, program, config or output, a null entry of columns, or a null constants with
+ *     n_constants > 0; INVALID_ARGUMENT for a size or count outside its limit, an unknown opcode, a
+ *     column, constant or output index out of range, a pop from an empty stack, a depth above 8, an
+ *     output emitted twice or never, a stack that is not empty after the last op.
+ *     mbls_fr_expr_check applies exactly the program rules: it is the same function.
+ *   overlap: output must not overlap any column (a rotated read of a row another lane has already
+ *     written); undefined.
+ *   timing: no branch and no address depends on a field value; the program and the rotations are
+ *     public.                                                                                    */
+/* ------------------------------------------------------------------------------------ */
+typedef enum {
+    MBLS_EXPR_COLUMN = 0, /* push columns[a][(i + b * rot_stride) mod size]   (b signed)  */
+    MBLS_EXPR_CONST  = 1, /* push constants[a]                                            */
+    MBLS_EXPR_ADD    = 2, /* pop y, pop x, push x + y                                     */
+    MBLS_EXPR_SUB    = 3, /* pop y, pop x, push x - y                                     */
+    MBLS_EXPR_MUL    = 4, /* pop y, pop x, push x * y                                     */
+    MBLS_EXPR_NEG    = 5, /* top = -top                                                   */
+    MBLS_EXPR_DOUBLE = 6, /* top = 2 top                                                  */
+    MBLS_EXPR_SQUARE = 7, /* top = top^2                                                  */
+    MBLS_EXPR_SCALE  = 8, /* top = top * constants[a]                                     */
+    MBLS_EXPR_HORNER = 9, /* pop t, pop acc, push acc * constants[a] + t                  */
+    MBLS_EXPR_EMIT   = 10 /* pop v, output[a * size + i] = v                              */
+} mbls_fr_expr_opcode;
+typedef struct { int32_t op, a, b; } mbls_fr_expr_op;   /* b is read by COLUMN only */
+
+eIcicleError mbls_fr_eval_program(const mbls_fr_t* const* columns, int n_columns, size_t size, size_t rot_stride,
+                                  const mbls_fr_t* constants, int n_constants,
+                                  const mbls_fr_expr_op* program, int n_ops, int n_outputs,
+                                  const VecOpsConfig* config, mbls_fr_t* output);
+/* host only, no device work: validates and describes a program.
+ * out[0] = maximum stack depth, out[1] = COLUMN loads per row, out[2] = field multiplications per row
+ * (MUL, SQUARE, SCALE, HORNER), out[3] = distinct (column, rotation) pairs. */
+eIcicleError mbls_fr_expr_check(const mbls_fr_expr_op* program, int n_ops, int n_columns, int n_constants,
+                                int n_outputs, int32_t* out);
+
+/* ------------------------------------------------------------------------------------ */
 /* batch point-form conversions, reference point_ops.cu:759 / :844 / :924 (exported there as
  * extern "C").  Montgomery in, Montgomery out; Jacobian projective (x = X/Z^2, y = Y/Z^3).
  * affine_to_projective: (x, y) -> (x, y, 1), identity (0, 0) -> (0, 1, 0).

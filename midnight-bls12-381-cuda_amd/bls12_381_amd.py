@@ -83,6 +83,7 @@ EXPORTED = [
     "mbls_g1_check_points", "mbls_g2_check_points",
     "mbls_g1_decompress", "mbls_g2_decompress", "mbls_g1_compress", "mbls_g2_compress",
     "mbls_fr_prefix_product", "mbls_fr_poly_divide_linear", "mbls_fr_scan_geometry",
+    "mbls_fr_eval_program", "mbls_fr_expr_check",
 ]
 
 _LIB = None
@@ -137,6 +138,8 @@ def lib():
         "mbls_g1_compress": [P, i32, b, P, P], "mbls_g2_compress": [P, i32, b, P, P],
         "mbls_fr_prefix_product": [P, P, sz, P, b, P, P, P], "mbls_fr_poly_divide_linear": [P, sz, P, P, P, P],
         "mbls_fr_scan_geometry": [sz, P],
+        "mbls_fr_eval_program": [P, i32, sz, sz, P, i32, P, i32, i32, P, P],
+        "mbls_fr_expr_check": [P, i32, i32, i32, i32, P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -489,6 +492,53 @@ def poly_divide_linear(coeffs, z, *, batch=1, out=None, quotient=True, eval=True
     check(lib().mbls_fr_poly_divide_linear(_p(coeffs), n, _p(z), ctypes.byref(cfg), _p(out), _p(eval)),
           "mbls_fr_poly_divide_linear")
     return out, eval
+
+
+# ----------------------------------------------------------------------------- expression evaluator
+(EXPR_COLUMN, EXPR_CONST, EXPR_ADD, EXPR_SUB, EXPR_MUL, EXPR_NEG, EXPR_DOUBLE, EXPR_SQUARE, EXPR_SCALE, EXPR_HORNER,
+ EXPR_EMIT) = range(11)
+EXPR_CHECK_FIELDS = ("depth", "loads", "muls", "pairs")
+
+
+class ExprOp(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_int32), ("a", ctypes.c_int32), ("b", ctypes.c_int32)]
+
+
+def _expr_program(program):
+    ops = (ExprOp * max(len(program), 1))()
+    for k, (op, a, b) in enumerate(program):
+        ops[k].op, ops[k].a, ops[k].b = int(op), int(a), int(b)
+    return ops
+
+
+def expr_check(program, n_columns, n_constants, n_outputs):
+    """validate and describe a program of (op, a, b) tuples (mbls_fr_expr_check; host only): dict of
+    EXPR_CHECK_FIELDS -- maximum stack depth, COLUMN loads per row, field multiplications per row,
+    distinct (column, rotation) pairs.  Raises IcicleError(INVALID_ARGUMENT) for a malformed one."""
+    out = (ctypes.c_int32 * len(EXPR_CHECK_FIELDS))()
+    check(lib().mbls_fr_expr_check(_expr_program(program), len(program), n_columns, n_constants, n_outputs, out),
+          "mbls_fr_expr_check")
+    return dict(zip(EXPR_CHECK_FIELDS, list(out)))
+
+
+def eval_program(columns, program, *, constants=None, n_outputs=1, rot_stride=1, out=None, stream=None, is_async=False):
+    """Run `program`, a list of (op, a, b) tuples of EXPR_* opcodes, once per row (mbls_fr_eval_program).
+    columns: a list of (n, 4) uint64 Montgomery columns, all numpy (host) or all torch (device);
+    COLUMN a, b reads columns[a][(i + b * rot_stride) mod n].  constants (k, 4), numpy or torch.
+    Returns out, (n_outputs * n, 4) with output k at rows k * n .. (k + 1) * n: `out` when given (it may
+    overlap no column), else placed as the columns are."""
+    n = columns[0].shape[0]
+    on_dev = _is_dev(columns[0])
+    assert all(c.shape[0] == n and _is_dev(c) == on_dev for c in columns), "columns share one size and placement"
+    if out is None:
+        out = _like(columns[0], n_outputs * n)
+    table = (ctypes.c_void_p * len(columns))(*[_p(c) for c in columns])
+    cfg = vec_config(is_a_on_device=on_dev, is_b_on_device=_is_dev(constants), is_result_on_device=_is_dev(out),
+                     is_async=is_async, stream=stream)
+    check(lib().mbls_fr_eval_program(table, len(columns), n, rot_stride, _p(constants),
+                                     0 if constants is None else constants.shape[0], _expr_program(program), len(program),
+                                     n_outputs, ctypes.byref(cfg), _p(out)), "mbls_fr_eval_program")
+    return out
 
 
 # ----------------------------------------------------------------------------- NTT
