@@ -75,9 +75,8 @@ MBLS_DEV uint8_t check_g1(const uint8_t* __restrict__ points, uint32_t i) {
     if (acc.is_inf()) return MBLS_POINT_OFF_SUBGROUP;  // phi(P) is not the identity
     // (X, Y, Z) == (beta x, y): both sides of each equation to canonical words.  acc.z has limbs
     // < 2^29 (J28's invariant) against normalised partners, as in madd.
-    Fq bw, lw, rw;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) bw.v[k] = GLV_BETA_MONT[k];
+    const Fq bw = glv_beta();
+    Fq lw, rw;
     to_words(acc.z, lw.v);
     if (lw.is_zero()) return MBLS_POINT_OFF_SUBGROUP;
     const F28 zz = sqr(acc.z);

@@ -59,9 +59,9 @@ class Arena {
 struct StreamCtx {
     int device = 0;
     Arena arena;
-    // side streams for latency-bound work that overlaps the main chain (MSM tree sums, the
-    // endomorphism table); forked from / joined back into the caller's stream with events, so
-    // callers see one stream-ordered operation
+    // side streams for work that overlaps the main chain (a batched MSM's tails and fronts,
+    // msm_call); forked from / joined back into the caller's stream with events, so callers see
+    // one stream-ordered operation.  Created on first use: a single MSM needs none
     std::vector<hipStream_t> sides;
     std::vector<hipEvent_t> events;
     hipEvent_t done = nullptr;  // recorded on the caller's stream when a call's enqueue ends

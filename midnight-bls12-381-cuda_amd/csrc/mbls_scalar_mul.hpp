@@ -111,10 +111,7 @@ MBLS_DEV J28 g1_glv_mul(const Affine<Fq>& b, const uint8_t* __restrict__ scalars
     glv_split(load_scalar<MONT>(scalars, si), m0, neg0, m1, neg1);
     add_eights(m0);
     add_eights(m1);
-    Fq bw;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) bw.v[k] = GLV_BETA_MONT[k];
-    const F28 beta = unpack_shift8(bw.v);
+    const F28 beta = unpack_shift8(glv_beta().v);
     acc = J28::inf();
 #pragma unroll 1
     for (int w = 0; w < 32; ++w) {

@@ -163,6 +163,12 @@ MBLS_DEV void glv_split(const Fr& s, uint32_t (&m1)[4], bool& neg1, uint32_t (&m
 static __constant__ uint32_t GLV_BETA_MONT[12] = {0x8671f071u, 0xcd03c9e4u, 0x1fcda5d2u, 0x5dab2246u,
                                                   0xd3851b95u, 0x587042afu, 0x01bacb9eu, 0x8eb60ebeu,
                                                   0x83d050d2u, 0x03f97d6eu, 0x54638741u, 0x18f02065u};
+MBLS_DEV Fq glv_beta() {
+    Fq beta;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) beta.v[k] = GLV_BETA_MONT[k];
+    return beta;
+}
 
 // ------------------------------------------------------------------------------------
 // psi split (G2): s == sum_j (-1)^neg_j m_j psi^j(Q) on G2, m_j < 2^63

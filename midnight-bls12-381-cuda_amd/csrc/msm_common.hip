@@ -1,6 +1,7 @@
-// msm_common.hip -- group-independent MSM stages: plan and reduction schedule, endomorphism
-// splits, signed digits and the two sorts (partitioned counting sort for c <= 16; atomic ranks,
-// scan and scatter for c > 16), chunking, synthetic scalars.
+// msm_common.hip -- group-independent MSM stages: plan and reduction schedule, and the front of an
+// MSM behind one call (msm_front): endomorphism splits with their per-call image tables, signed
+// digits and the two sorts (partitioned counting sort for c <= 16, every split plan included;
+// atomic ranks, scan and scatter for unsplit c > 16), chunk tables.  Synthetic scalars.
 //
 // Reference: get_optimal_c (msm.cuh:115-133), compute_bucket_indices_kernel
 // (msm_kernels.cu:69-143), histogram (:224-256), cub ExclusiveSum / SortPairs (:748-781).
@@ -163,6 +164,9 @@ eIcicleError make_plan(long long n, const MSMConfig* cfg, MsmPlan& p, int endo) 
     p.table = p.prepared ? p.split : p.bstride > 1 ? p.bstride : F;  // bases-buffer entries per point
     p.contributions = (size_t)n * W * p.split;
     if (p.pts >= (1u << 31)) return MBLS_INVALID_ARGUMENT;
+    // the split digit sources and the per-call image tables exist only on the partitioned sort
+    // (c <= 16, which the rules above give every split plan)
+    if (p.split > 1 && !partition_sort(p)) return MBLS_INVALID_ARGUMENT;
     return plan_levels(p, Wg);
 }
 
@@ -391,8 +395,9 @@ MBLS_DEV void window_span(int j, int c, int Wg, int sF, int& pos, int& wid) {
 //    split) live in mbls_split.hpp with the GLV and psi splits, shared with scalar_mul.hip.
 
 // ------------------------------------------------------------------------------------
-// 1. digits, c > 16 (the atomic-rank sort: k_digits / k_digits_glv, the scan of section 2 and
-//    k_scatter of section 3): one thread per scalar
+// 1. digits, c > 16 (the atomic-rank sort: k_digits, the scan of section 2 and k_scatter of
+//    section 3): one thread per scalar.  Unsplit plans only: make_plan keeps every split plan at
+//    c <= 16, the partitioned sort of section 2b.
 // ------------------------------------------------------------------------------------
 template <bool MONT>
 __global__ __launch_bounds__(256) void k_digits(const uint8_t* __restrict__ scalars, uint32_t n, int c, int W, int Wg, int sF, uint32_t F,
@@ -432,67 +437,6 @@ __global__ __launch_bounds__(256) void k_digits(const uint8_t* __restrict__ scal
     // c = 7..16 in tests/test_oracle.py)
 }
 
-// ------------------------------------------------------------------------------------
-// 1b. GLV digits (G1): s = +-m1 +- m2*lam (mod r), m1, m2 < 2^127 (oracle/pyref.py
-//     glv_decompose), lam = z^2 - 1 and r = lam^2 + lam + 1.  Point index i carries the m1
-//     digits, index n + i (the phi(P_i) table) the m2 digits; both halves share each window's
-//     buckets, so the windows halve (255 -> 127 bits) at the same contribution count.
-//     glv_split and its constants: mbls_split.hpp.
-// ------------------------------------------------------------------------------------
-template <bool MONT>
-__global__ __launch_bounds__(256) void k_digits_glv(const uint8_t* __restrict__ scalars, uint32_t n, int c, int W,
-                                                    uint32_t B, uint32_t* __restrict__ keys,
-                                                    uint32_t* __restrict__ vals, uint32_t* __restrict__ ranks,
-                                                    uint32_t* __restrict__ counts, SplitLayout lay) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Fr s = load_scalar<MONT>(scalars, i);
-    uint32_t m[2][4];
-    bool neg[2];
-    glv_split(s, m[0], neg[0], m[1], neg[1]);
-    const uint32_t mask = (1u << c) - 1;
-    const size_t stride = 2 * (size_t)n;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        uint32_t carry = 0;
-        for (int w = 0; w < W; ++w) {
-            const int bit = w * c;
-            const int word = bit >> 5, sh = bit & 31;
-            uint32_t lo = 0, hi = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                lo = (k == word) ? m[h][k] : lo;
-                hi = (k == word + 1) ? m[h][k] : hi;
-            }
-            uint64_t win = ((uint64_t)hi << 32) | lo;
-            uint32_t v = ((uint32_t)(win >> sh) & mask) + carry;
-            carry = 0;
-            uint32_t sign = neg[h] ? 1u : 0u;
-            if (v > B) {
-                v = (1u << c) - v;
-                sign ^= 1u;
-                carry = 1;
-            }
-            const uint32_t idx = lay.at(h, i);
-            emit_digit(v ? (uint32_t)w * B + (v - 1) : INVALID_KEY, (idx << 1) | sign, (size_t)w * stride + idx, keys,
-                       vals, ranks, counts);
-        }
-    }
-}
-
-// phi table: phi[i] = (beta x_i, y_i) (Montgomery); identity (0, 0) maps to itself
-// (GLV_BETA_MONT: mbls_split.hpp)
-__global__ void k_glv_table(const uint8_t* __restrict__ bases, uint8_t* __restrict__ phi, uint32_t n) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Fq beta;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) beta.v[k] = GLV_BETA_MONT[k];
-    Affine<Fq> p = load_affine<Fq>(bases, i);
-    p.x = p.x * beta;
-    store_affine<Fq>(phi, i, p);
-}
-
 // Host operands of an MSM (core/msm.rs:665,773 pass a HostSlice).  Page-locked host memory is
 // read by a kernel through its device alias (PCIe reads by every CU, 4 x 16 B in flight per
 // lane); hipMemcpyAsync from pinned memory ran at ~28 GB/s for the 32 MiB of a 2^20 MSM's scalars
@@ -527,21 +471,29 @@ eIcicleError stage_to_device(void* dst, const void* src, size_t bytes, hipStream
     return MBLS_SUCCESS;
 }
 
-eIcicleError launch_glv_table(const uint8_t* bases, uint8_t* phi, uint32_t n, hipStream_t st) {
-    hipLaunchKernelGGL(k_glv_table, dim3((n + 255) / 256), dim3(256), 0, st, bases, phi, n);
-    MBLS_TRY(hipGetLastError());
-    return MBLS_SUCCESS;
+// ------------------------------------------------------------------------------------
+// 1b. endomorphism splits: one scalar into the digit sources of its streams, one sign-magnitude
+//     uint4 per stream (bit 127 = sign), at the stream's point index lay.at(j, i): j n + i against
+//     the per-call image table, i S + j against a prepared point-major table.
+//     GLV (G1): s = +-m1 +- m2*lam (mod r), m1, m2 < 2^127 (oracle/pyref.py glv_decompose),
+//     lam = z^2 - 1 and r = lam^2 + lam + 1; stream 1 multiplies phi(P_i).  Both halves share
+//     each window's buckets, so the windows halve (255 -> 127 bits) at the same contribution count.
+//     psi (G2): s == sum_j (-1)^neg_j m_j psi^j(Q) on G2, m_j < 2^63 (oracle/pyref.py
+//     psi_decompose).  psi = [z] on G2 and r = x^4 - x^2 + 1 for x = |z|, so balanced base-x
+//     digits d_j (|d_j| <= x/2) plus the carry d_4 folded back with x^4 == x^2 - 1 give
+//     s == sum_j d_j x^j == sum_j (-1)^j d_j z^j; stream j multiplies psi^j(P_i).
+//     The splits themselves (glv_split, psi_split, divmod_x) and their constants: mbls_split.hpp.
+// ------------------------------------------------------------------------------------
+template <bool MONT>
+MBLS_DEV void glv_split_one(const uint8_t* __restrict__ scalars, uint4* __restrict__ out, uint32_t i, SplitLayout lay) {
+    Fr s = load_scalar<MONT>(scalars, i);
+    uint32_t m1[4], m2[4];
+    bool n1, n2;
+    glv_split(s, m1, n1, m2, n2);
+    out[lay.at(0, i)] = make_uint4(m1[0], m1[1], m1[2], m1[3] | (n1 ? 0x80000000u : 0u));
+    out[lay.at(1, i)] = make_uint4(m2[0], m2[1], m2[2], m2[3] | (n2 ? 0x80000000u : 0u));
 }
 
-// ------------------------------------------------------------------------------------
-// 1b'. psi split (G2): s == sum_j (-1)^neg_j m_j psi^j(Q) on G2, m_j < 2^63
-//      (oracle/pyref.py psi_decompose).  psi = [z] on G2 and r = x^4 - x^2 + 1 for x = |z|,
-//      so balanced base-x digits d_j (|d_j| <= x/2) plus the carry d_4 folded back with
-//      x^4 == x^2 - 1 give s == sum_j d_j x^j == sum_j (-1)^j d_j z^j.
-//      Point index j*n + i carries psi^j(P_i) (k_psi_table); the digit source per index is
-//      one uint4 in the GLV format (magnitude words 0-1, bit 127 = sign).
-//      The split itself (psi_split, divmod_x): mbls_split.hpp.
-// ------------------------------------------------------------------------------------
 template <bool MONT>
 MBLS_DEV void psi_split_one(const uint8_t* __restrict__ scalars, uint32_t n, uint4* __restrict__ out, uint32_t i,
                             SplitLayout lay) {
@@ -583,8 +535,7 @@ MBLS_DEV void block_rows_out(uint8_t* __restrict__ dst, const uint4* __restrict_
 // the block's rows of the three psi tables (table j at (j - 1) n), through one 48 KB stage.
 // bstride > 1: the bases are slot 0 of a precomputed table with bstride entries per point
 // (plan.bstride); the compact copy of the points goes first, [P, psi P, psi^2 P, psi^3 P] (4n rows)
-MBLS_DEV void psi_block(const uint8_t* __restrict__ bases, uint8_t* __restrict__ phi, uint32_t n,
-                        uint32_t bstride = 1) {
+MBLS_DEV void psi_block(const uint8_t* __restrict__ bases, uint8_t* __restrict__ phi, uint32_t n, uint32_t bstride) {
     __shared__ uint4 stage[256 * 12];
     const uint32_t b0 = blockIdx.x * blockDim.x, i = b0 + threadIdx.x;
     const uint32_t rows = min(blockDim.x, n - b0);
@@ -606,10 +557,6 @@ MBLS_DEV void psi_block(const uint8_t* __restrict__ bases, uint8_t* __restrict__
         if (i < n) store_affine<Fq2>(stage, threadIdx.x, q[j]);
         block_rows_out<192>(phi + ((size_t)j * n + b0) * 192, stage, rows);
     }
-}
-
-__global__ __launch_bounds__(256) void k_psi_table(const uint8_t* __restrict__ bases, uint8_t* __restrict__ phi, uint32_t n) {
-    psi_block(bases, phi, n);
 }
 
 // G2 front in one launch (the psi counterpart of k_glv_prep): thread i splits scalar i and
@@ -638,10 +585,7 @@ __global__ __launch_bounds__(256) void k_endo_table_g1(const uint8_t* __restrict
     if (i < n) {
         Affine<Fq> p = load_affine<Fq>(in, i);
         store_affine<Fq>(stage, 2 * threadIdx.x, p);
-        Fq beta;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) beta.v[k] = GLV_BETA_MONT[k];
-        p.x = p.x * beta;
+        p.x = p.x * glv_beta();
         store_affine<Fq>(stage, 2 * threadIdx.x + 1, p);
     }
     block_rows_out<192>(out + (size_t)b0 * 192, stage, min(blockDim.x, n - b0));
@@ -674,17 +618,12 @@ eIcicleError launch_endo_table(const uint8_t* in, uint8_t* out, uint32_t n, int 
     return MBLS_SUCCESS;
 }
 
-eIcicleError launch_psi_table(const uint8_t* bases, uint8_t* phi, uint32_t n, hipStream_t st) {
-    hipLaunchKernelGGL(k_psi_table, dim3((n + 255) / 256), dim3(256), 0, st, bases, phi, n);
-    MBLS_TRY(hipGetLastError());
-    return MBLS_SUCCESS;
-}
-
 // ------------------------------------------------------------------------------------
 // 1c. digit sources of the partitioned sort (c <= 16, section 2b): the split kernels write NW
 //     words per index (GLV halves / psi quarters: 4 words, bit 127 = sign; plain: 8 words),
-//     which k_digits_part reads a tile of DT_TILE indices at a time.  c > 16 keeps k_digits /
-//     k_digits_glv above: global-atomic ranks, the three-kernel scan and k_scatter.
+//     which k_digits_part reads a tile of DT_TILE indices at a time.  With a per-call image
+//     table the split kernel writes the table's rows as well (k_glv_prep, k_psi_prep).  c > 16
+//     keeps k_digits above: global-atomic ranks, the three-kernel scan and k_scatter.
 // ------------------------------------------------------------------------------------
 static constexpr int DT_THREADS = 1024;
 #ifndef MBLS_DT_PER
@@ -704,17 +643,12 @@ __global__ __launch_bounds__(256) void k_glv_split(const uint8_t* __restrict__ s
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     z.run(i, gridDim.x * blockDim.x);
     if (i >= n) return;
-    Fr s = load_scalar<MONT>(scalars, i);
-    uint32_t m1[4], m2[4];
-    bool n1, n2;
-    glv_split(s, m1, n1, m2, n2);
-    out[lay.at(0, i)] = make_uint4(m1[0], m1[1], m1[2], m1[3] | (n1 ? 0x80000000u : 0u));
-    out[lay.at(1, i)] = make_uint4(m2[0], m2[1], m2[2], m2[3] | (n2 ? 0x80000000u : 0u));
+    glv_split_one<MONT>(scalars, out, i, lay);
 }
 
-// G1 front in one launch: thread i splits scalar i (k_glv_split) AND writes phi(P_i) (k_glv_table)
-// -- the table no longer runs on a side stream beside the digit / sort front (its fork / join
-// event waits and its contention with k_glv_split cost more than its own time)
+// G1 front in one launch: thread i splits scalar i (k_glv_split) AND writes phi(P_i) = (beta x_i,
+// y_i) -- a table kernel on a side stream beside the digit / sort front cost more than its own
+// time (its fork / join event waits and its contention with k_glv_split)
 template <bool MONT>
 // bstride > 1: the bases are slot 0 of a precomputed table with bstride entries per point
 // (plan.bstride, make_plan); the kernel then writes the compact [P_0..P_(n-1), phi(P_0)..] into
@@ -738,21 +672,13 @@ __global__ __launch_bounds__(256) void k_glv_prep(const uint8_t* __restrict__ sc
             phi_rows = phi + (size_t)n * 96;
         }
         if (i < n) {
-            Fq beta;
-#pragma unroll
-            for (int k = 0; k < 12; ++k) beta.v[k] = GLV_BETA_MONT[k];
-            p.x = p.x * beta;
+            p.x = p.x * glv_beta();
             store_affine<Fq>(stage, threadIdx.x, p);
         }
         block_rows_out<96>(phi_rows + (size_t)b0 * 96, stage, rows);
     }
     if (i >= n) return;
-    Fr s = load_scalar<MONT>(scalars, i);
-    uint32_t m1[4], m2[4];
-    bool n1, n2;
-    glv_split(s, m1, n1, m2, n2);
-    out[i] = make_uint4(m1[0], m1[1], m1[2], m1[3] | (n1 ? 0x80000000u : 0u));
-    out[n + i] = make_uint4(m2[0], m2[1], m2[2], m2[3] | (n2 ? 0x80000000u : 0u));
+    glv_split_one<MONT>(scalars, out, i, SplitLayout{n, 1});
 }
 
 __global__ void k_scalars_std(const uint8_t* __restrict__ scalars, uint32_t n, uint8_t* __restrict__ out, ZeroList z) {
@@ -770,76 +696,55 @@ size_t digits_src_bytes(uint32_t n, int split) { return (size_t)n * (split == 4 
 __global__ void k_zero_list(ZeroList z) { z.run(blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x); }
 
 // the MSM's first kernel also clears the words later kernels accumulate into (ZeroList): a
-// separate hipMemsetAsync is a fill kernel of its own, ~9-18 us on the critical path each
-static eIcicleError digit_sources(const uint8_t* scalars, bool mont, uint32_t n, const MsmPlan& P, uint8_t* dsrc,
-                                  const ZeroList& z, hipStream_t st, const uint32_t*& src, uint32_t& nidx,
-                                  const uint8_t* bases, uint8_t* phi) {
-    dim3 g((n + 255) / 256);
+// separate hipMemsetAsync is a fill kernel of its own, ~9-18 us on the critical path each.
+// With a per-call image table (S.phi) the split kernel writes the table too.
+static eIcicleError digit_sources(const uint8_t* scalars, bool mont, const uint8_t* bases, uint32_t n,
+                                  const MsmPlan& P, const MsmScratch& S, const ZeroList& z, hipStream_t st,
+                                  const uint32_t*& src, uint32_t& nidx) {
+    const dim3 g((n + 255) / 256), b(256);
+    uint4* out = (uint4*)S.dsrc;
+    const uint32_t bstride = (uint32_t)P.bstride;
     // digit-source (= point) index of stream j of scalar i: j n + i against the per-call image
     // table, i S + j against a prepared point-major table [P, phi P] / [P, psi P, psi^2 P, psi^3 P]
     const SplitLayout lay = P.prepared ? SplitLayout{1u, (uint32_t)P.split} : SplitLayout{n, 1u};
-    if (P.split == 2 && phi) {  // split + phi table fused (k_glv_prep)
-        if (mont)
-            hipLaunchKernelGGL(k_glv_prep<true>, g, dim3(256), 0, st, scalars, n, (uint4*)dsrc, z, bases, phi,
-                               (uint32_t)P.bstride);
-        else
-            hipLaunchKernelGGL(k_glv_prep<false>, g, dim3(256), 0, st, scalars, n, (uint4*)dsrc, z, bases, phi,
-                               (uint32_t)P.bstride);
-        src = (const uint32_t*)dsrc;
-        nidx = 2 * n;
+    src = (const uint32_t*)S.dsrc;
+    nidx = n * (uint32_t)P.split;
+#define MBLS_SPLIT(K_, ...)                                                               \
+    if (mont)                                                                             \
+        hipLaunchKernelGGL(K_<true>, g, b, 0, st, scalars, n, out, z, __VA_ARGS__);       \
+    else                                                                                  \
+        hipLaunchKernelGGL(K_<false>, g, b, 0, st, scalars, n, out, z, __VA_ARGS__)
+    if (P.split == 2 && S.phi) {
+        MBLS_SPLIT(k_glv_prep, bases, S.phi, bstride);
     } else if (P.split == 2) {
-        if (mont)
-            hipLaunchKernelGGL(k_glv_split<true>, g, dim3(256), 0, st, scalars, n, (uint4*)dsrc, z, lay);
-        else
-            hipLaunchKernelGGL(k_glv_split<false>, g, dim3(256), 0, st, scalars, n, (uint4*)dsrc, z, lay);
-        src = (const uint32_t*)dsrc;
-        nidx = 2 * n;
-    } else if (P.split == 4 && phi) {  // split + psi table fused (k_psi_prep)
-        if (mont)
-            hipLaunchKernelGGL(k_psi_prep<true>, g, dim3(256), 0, st, scalars, n, (uint4*)dsrc, z, bases, phi,
-                               (uint32_t)P.bstride);
-        else
-            hipLaunchKernelGGL(k_psi_prep<false>, g, dim3(256), 0, st, scalars, n, (uint4*)dsrc, z, bases, phi,
-                               (uint32_t)P.bstride);
-        src = (const uint32_t*)dsrc;
-        nidx = 4 * n;
+        MBLS_SPLIT(k_glv_split, lay);
+    } else if (P.split == 4 && S.phi) {
+        MBLS_SPLIT(k_psi_prep, bases, S.phi, bstride);
     } else if (P.split == 4) {
-        if (mont)
-            hipLaunchKernelGGL(k_psi_split<true>, g, dim3(256), 0, st, scalars, n, (uint4*)dsrc, z, lay);
-        else
-            hipLaunchKernelGGL(k_psi_split<false>, g, dim3(256), 0, st, scalars, n, (uint4*)dsrc, z, lay);
-        src = (const uint32_t*)dsrc;
-        nidx = 4 * n;
-    } else {
-        if (mont)
-            hipLaunchKernelGGL(k_scalars_std, g, dim3(256), 0, st, scalars, n, dsrc, z);
-        else
-            hipLaunchKernelGGL(k_zero_list, dim3(8), dim3(256), 0, st, z);
-        src = (const uint32_t*)(mont ? dsrc : scalars);
-        nidx = n;
+        MBLS_SPLIT(k_psi_split, lay);
+    } else if (mont) {
+        hipLaunchKernelGGL(k_scalars_std, g, b, 0, st, scalars, n, S.dsrc, z);
+    } else {  // standard scalars are read in place
+        hipLaunchKernelGGL(k_zero_list, dim3(8), b, 0, st, z);
+        src = (const uint32_t*)scalars;
     }
+#undef MBLS_SPLIT
     MBLS_TRY(hipGetLastError());
     return MBLS_SUCCESS;
 }
 
-eIcicleError launch_digits(const uint8_t* scalars, bool mont, uint32_t n, const MsmPlan& P, uint32_t* keys,
-                           uint32_t* vals, uint32_t* ranks, uint32_t* counts, hipStream_t st) {
-    dim3 g((n + 255) / 256);
-    if (P.split == 4) return MBLS_INVALID_ARGUMENT;  // make_plan keeps psi to c <= 16
-    if (P.split == 2) {
-        const SplitLayout lay = P.prepared ? SplitLayout{1u, 2u} : SplitLayout{n, 1u};
-        if (mont)
-            hipLaunchKernelGGL(k_digits_glv<true>, g, dim3(256), 0, st, scalars, n, P.c, P.W, P.B, keys, vals, ranks, counts,
-                               lay);
-        else
-            hipLaunchKernelGGL(k_digits_glv<false>, g, dim3(256), 0, st, scalars, n, P.c, P.W, P.B, keys, vals, ranks,
-                               counts, lay);
-    } else if (mont)
-        hipLaunchKernelGGL(k_digits<true>, g, dim3(256), 0, st, scalars, n, P.c, P.W, P.Wg, P.sF, (uint32_t)P.F, P.B, keys,
-                           vals, ranks, counts);
+// c > 16: digits as (key, value) pairs with global-atomic ranks, into the zeroed bucket histogram
+static eIcicleError launch_digits(const uint8_t* scalars, bool mont, uint32_t n, const MsmPlan& P, const MsmScratch& S,
+                                  hipStream_t st) {
+    if (P.split > 1) return MBLS_INVALID_ARGUMENT;  // make_plan keeps the splits on the partitioned sort
+    const dim3 g((n + 255) / 256), b(256);
+    MBLS_TRY(hipMemsetAsync(S.counts, 0, (size_t)P.TB * 4, st));
+    if (mont)
+        hipLaunchKernelGGL(k_digits<true>, g, b, 0, st, scalars, n, P.c, P.W, P.Wg, P.sF, (uint32_t)P.F, P.B, S.keys,
+                           S.vals, S.ranks, S.counts);
     else
-        hipLaunchKernelGGL(k_digits<false>, g, dim3(256), 0, st, scalars, n, P.c, P.W, P.Wg, P.sF, (uint32_t)P.F, P.B, keys,
-                           vals, ranks, counts);
+        hipLaunchKernelGGL(k_digits<false>, g, b, 0, st, scalars, n, P.c, P.W, P.Wg, P.sF, (uint32_t)P.F, P.B, S.keys,
+                           S.vals, S.ranks, S.counts);
     MBLS_TRY(hipGetLastError());
     return MBLS_SUCCESS;
 }
@@ -912,7 +817,7 @@ __global__ __launch_bounds__(256) void k_scan_add(uint32_t* __restrict__ out, co
 
 size_t scan_tmp_words(uint32_t m) { return (m + SCAN_BLOCK - 1) / SCAN_BLOCK + 8; }
 
-eIcicleError scan_exclusive(const uint32_t* in, uint32_t* out, uint32_t m, uint32_t* tmp, hipStream_t st) {
+static eIcicleError scan_exclusive(const uint32_t* in, uint32_t* out, uint32_t m, uint32_t* tmp, hipStream_t st) {
     uint32_t nb = (m + SCAN_BLOCK - 1) / SCAN_BLOCK;
     hipLaunchKernelGGL(k_scan_local, dim3(nb), dim3(256), 0, st, in, out, tmp, m);
     hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, st, tmp, nb, tmp + nb);
@@ -940,6 +845,16 @@ static int part_fine_bits(uint32_t B) {
 }
 
 bool partition_sort(const MsmPlan& P) { return P.B <= DT_MAX_B; }
+
+// chunk counts computed by the partition sort itself (k_part_sort, parts of 128 fine buckets):
+// k_chunk_counts' outputs with the prefixes in blocks of 128 buckets (CHUNK_FUSED_SHIFT)
+struct ChunkCountOut {
+    uint32_t* nchunks = nullptr;  // null: not fused (k_part_sort writes the bucket counts)
+    uint32_t* binhist = nullptr;  // order histograms (accumulated: zeroed by the digit pass)
+    uint32_t* blk_tot = nullptr;  // per 128-bucket block: the chunk-count total
+    uint32_t L = 0, m = 0;        // chunk length, bucket count
+};
+static constexpr int CHUNK_FUSED_SHIFT = 7;
 
 PartSortSizes part_sort_sizes(const MsmPlan& P) {
     PartSortSizes s;
@@ -1557,29 +1472,28 @@ __global__ __launch_bounds__(PS_THREADS) void k_part_sort(const uint32_t* __rest
     }
 }
 
-eIcicleError launch_digits_part(const uint8_t* scalars, bool mont, uint32_t n, const MsmPlan& P, uint32_t* ent,
-                                uint32_t* seg_off, uint32_t* seg_cnt, uint32_t* part_tot, uint8_t* dsrc,
-                                uint32_t* zero_word, hipStream_t st, const uint8_t* bases, uint8_t* phi,
-                                uint32_t* zero2, uint32_t nzero2) {
-    if (P.B > DT_MAX_B) return MBLS_INVALID_ARGUMENT;
+// pass A with its digit sources; fused_cc: the digit pass also clears the order histograms that
+// k_part_sort accumulates its chunk counts into
+static eIcicleError launch_digits_part(const uint8_t* scalars, bool mont, const uint8_t* bases, uint32_t n,
+                                       const MsmPlan& P, const MsmScratch& S, bool fused_cc, hipStream_t st) {
     const PartSortSizes z = part_sort_sizes(P);
     const uint32_t* src;
     uint32_t nidx;
     ZeroList zl;
-    zl.p[0] = part_tot;  // k_digits_part's per-part totals (atomics)
+    zl.p[0] = S.part_tot;  // k_digits_part's per-part totals (atomics)
     zl.n[0] = (uint32_t)P.Wg * z.NP;
-    zl.p[1] = zero_word;  // the chunk-count maximum (k_chunk_counts' atomicMax), HeavyTab counters
-    zl.n[1] = zero_word ? 3u : 0u;
-    zl.p[2] = zero2;  // the fused chunk-count order histograms (k_part_sort atomics)
-    zl.n[2] = zero2 ? nzero2 : 0u;
-    eIcicleError er = digit_sources(scalars, mont, n, P, dsrc, zl, st, src, nidx, bases, phi);
+    zl.p[1] = S.nchunks + P.TB;  // the chunk-count maximum (k_chunk_counts' atomicMax), HeavyTab counters
+    zl.n[1] = 3u;
+    zl.p[2] = fused_cc ? S.binhist : nullptr;  // the fused chunk-count order histograms (k_part_sort atomics)
+    zl.n[2] = fused_cc ? order_words(P.TB) : 0u;
+    eIcicleError er = digit_sources(scalars, mont, bases, n, P, S, zl, st, src, nidx);
     if (er != MBLS_SUCCESS) return er;
     dim3 g(z.segments), b(DT_THREADS);
     const uint32_t F = (uint32_t)P.F;
     const DigitOffset C = digit_offset(P.c, P.W, P.B, P.Wg, P.sF);
 #define MBLS_DP(S_, P_)                                                                                           \
-    hipLaunchKernelGGL((k_digits_part<S_, P_>), g, b, 0, st, src, nidx, P.c, P.Wg, P.sF, F, P.B, z.FB, z.NP, ent, seg_off, \
-                       seg_cnt, part_tot, C)
+    hipLaunchKernelGGL((k_digits_part<S_, P_>), g, b, 0, st, src, nidx, P.c, P.Wg, P.sF, F, P.B, z.FB, z.NP, S.ent, \
+                       S.seg_off, S.seg_cnt, S.part_tot, C)
     if (P.split > 1) {
         if (z.pack)
             MBLS_DP(true, true);
@@ -1594,33 +1508,23 @@ eIcicleError launch_digits_part(const uint8_t* scalars, bool mont, uint32_t n, c
     return MBLS_SUCCESS;
 }
 
-bool part_sort_fuses_chunks(const MsmPlan& P) { return part_fine_bits(P.B) == CHUNK_FUSED_SHIFT; }
-
-eIcicleError launch_part_sort(const MsmPlan& P, const uint32_t* ent, const uint32_t* seg_off, const uint32_t* seg_cnt,
-                              const uint32_t* part_tot, uint32_t* counts, uint32_t* offsets, uint32_t* sorted,
-                              const ChunkCountOut& cc, hipStream_t st, const PartHelp& hp_in) {
+// pass B behind the heavy parts' helper plan; writes the bucket counts -- or with cc.nchunks the
+// chunk counts and their prefixes (over S.counts) --, the offsets (offsets[TB] included) and sorted
+static eIcicleError launch_part_sort(const MsmPlan& P, const MsmScratch& S, const ChunkCountOut& cc, hipStream_t st) {
     const PartSortSizes z = part_sort_sizes(P);
-    if (cc.nchunks && z.FB != CHUNK_FUSED_SHIFT) return MBLS_INVALID_ARGUMENT;
     if (z.FB > 7) return MBLS_INVALID_ARGUMENT;  // 128 fine counters per part (cnt, pre, hh rows)
-    const bool help = hp_in.help && hp_in.hh && hp_in.hpart;
-    const PartHelp hp = help ? hp_in : PartHelp();
-    const uint32_t M = (uint32_t)P.Wg * z.NP;
-    dim3 g(M + (help ? PH_HELPERS : 0u)), b(PS_THREADS);
-    if (help) {
-        if (z.pack)
-            hipLaunchKernelGGL(k_part_heavy_count<true>, dim3(PH_HELPERS), b, 0, st, ent, seg_off, seg_cnt, part_tot,
-                               z.tiles, P.W, P.Wg, z.FB, z.NP, hp);
-        else
-            hipLaunchKernelGGL(k_part_heavy_count<false>, dim3(PH_HELPERS), b, 0, st, ent, seg_off, seg_cnt, part_tot,
-                               z.tiles, P.W, P.Wg, z.FB, z.NP, hp);
-        MBLS_TRY(hipGetLastError());
+    const dim3 g((uint32_t)P.Wg * z.NP + PH_HELPERS), b(PS_THREADS);
+    if (z.pack) {
+        hipLaunchKernelGGL(k_part_heavy_count<true>, dim3(PH_HELPERS), b, 0, st, S.ent, S.seg_off, S.seg_cnt, S.part_tot,
+                           z.tiles, P.W, P.Wg, z.FB, z.NP, S.ph);
+        hipLaunchKernelGGL(k_part_sort<true>, g, b, 0, st, S.ent, S.seg_off, S.seg_cnt, S.part_tot, z.tiles, P.W, P.Wg,
+                           P.B, z.FB, z.NP, S.counts, S.offsets, S.sorted, cc, S.ph);
+    } else {
+        hipLaunchKernelGGL(k_part_heavy_count<false>, dim3(PH_HELPERS), b, 0, st, S.ent, S.seg_off, S.seg_cnt, S.part_tot,
+                           z.tiles, P.W, P.Wg, z.FB, z.NP, S.ph);
+        hipLaunchKernelGGL(k_part_sort<false>, g, b, 0, st, S.ent, S.seg_off, S.seg_cnt, S.part_tot, z.tiles, P.W, P.Wg,
+                           P.B, z.FB, z.NP, S.counts, S.offsets, S.sorted, cc, S.ph);
     }
-    if (z.pack)
-        hipLaunchKernelGGL(k_part_sort<true>, g, b, 0, st, ent, seg_off, seg_cnt, part_tot, z.tiles, P.W, P.Wg, P.B,
-                           z.FB, z.NP, counts, offsets, sorted, cc, hp);
-    else
-        hipLaunchKernelGGL(k_part_sort<false>, g, b, 0, st, ent, seg_off, seg_cnt, part_tot, z.tiles, P.W, P.Wg, P.B,
-                           z.FB, z.NP, counts, offsets, sorted, cc, hp);
     MBLS_TRY(hipGetLastError());
     return MBLS_SUCCESS;
 }
@@ -1683,17 +1587,6 @@ __global__ __launch_bounds__(256) void k_chunk_counts(const uint32_t* counts, co
 // order alone gave ~4 +- 1.5 chunks per lane and a wave ran its maximum).  binbase = exclusive
 // scan of k_chunk_counts' histograms (order_index layout).
 
-eIcicleError launch_chunk_counts(const uint32_t* counts, const uint32_t* offsets, uint32_t* nchunks, uint32_t m,
-                                 uint32_t L, uint32_t* binhist, uint32_t groups, bool zeroed, uint32_t* cloc,
-                                 uint32_t* blk_tot, hipStream_t st) {
-    if (!zeroed) MBLS_TRY(hipMemsetAsync(nchunks + m, 0, 12, st));  // maximum + HeavyTab counters
-    const uint32_t nblk = (m + 255) / 256;
-    hipLaunchKernelGGL(k_chunk_counts, dim3(nblk), dim3(256), 0, st, counts, offsets, nchunks, m, L, binhist,
-                       nblk / groups, cloc, blk_tot);
-    MBLS_TRY(hipGetLastError());
-    return MBLS_SUCCESS;
-}
-
 uint32_t order_words(uint32_t m) { return ORDER_BINS * ((m + 255) / 256); }
 
 // exclusive scan of a short array in ONE workgroup of 1024 threads; out[m] = total
@@ -1752,14 +1645,6 @@ __global__ __launch_bounds__(1024) void k_scan_small(const uint32_t* __restrict_
     scan_wg(in2, out2, m2, wtot);
 }
 
-eIcicleError launch_order_scan(const uint32_t* binhist, uint32_t* binbase, uint32_t m, const uint32_t* blk_tot,
-                               uint32_t* blk_pre, uint32_t nblk, hipStream_t st) {
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, binhist, binbase, order_words(m), blk_tot, blk_pre,
-                       nblk);
-    MBLS_TRY(hipGetLastError());
-    return MBLS_SUCCESS;
-}
-
 // ------------------------------------------------------------------------------------
 // 3. scatter of the atomic-rank sort (c > 16)
 // ------------------------------------------------------------------------------------
@@ -1771,14 +1656,6 @@ __global__ __launch_bounds__(256) void k_scatter(const uint32_t* __restrict__ ke
     const uint32_t k = keys[i];
     if (k == INVALID_KEY) return;
     sorted[offsets[k] + ranks[i]] = vals[i];
-}
-
-eIcicleError launch_scatter(const uint32_t* keys, const uint32_t* vals, const uint32_t* ranks, size_t total,
-                            const uint32_t* offsets, uint32_t* sorted, hipStream_t st) {
-    hipLaunchKernelGGL(k_scatter, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, keys, vals, ranks, total,
-                       offsets, sorted);
-    MBLS_TRY(hipGetLastError());
-    return MBLS_SUCCESS;
 }
 
 // chunk_off[b] = cloc[b] + blk_pre[b >> cs] (the scan begun in k_chunk_counts or k_part_sort; chunk_off[m] =
@@ -1838,13 +1715,57 @@ __global__ __launch_bounds__(256) void k_chunk_owner(const uint32_t* __restrict_
     }
 }
 
-eIcicleError launch_chunk_owner(const uint32_t* cloc, const uint32_t* blk_pre, int cs, uint32_t* chunk_off,
-                                const uint32_t* offsets, uint32_t m, uint32_t L, uint32_t* owner, uint32_t* first,
-                                const uint32_t* nchunks, const uint32_t* binbase, uint32_t* perm, HeavyTab H,
-                                hipStream_t st) {
-    const uint32_t nblk = (m + 255) / 256;
-    hipLaunchKernelGGL(k_chunk_owner, dim3(nblk), dim3(256), 0, st, cloc, blk_pre, cs, chunk_off, offsets, m, L, owner,
-                       first, nchunks, binbase, perm, H);
+// ------------------------------------------------------------------------------------
+// 4. the front of one MSM
+// ------------------------------------------------------------------------------------
+eIcicleError msm_front(const uint8_t* scalars, bool scalars_mont, const uint8_t* bases, uint32_t n,
+                       const MsmPlan& P, const MsmScratch& S, hipStream_t st) {
+    const uint32_t TB = P.TB, blocks = (TB + 255) / 256;  // one thread per bucket
+    const bool psort = partition_sort(P);
+    // the partition sort of 128-bucket parts also computes the chunk counts (k_chunk_counts'
+    // outputs, prefixes in 128-bucket blocks): one launch fewer
+    const bool fused_cc = psort && part_fine_bits(P.B) == CHUNK_FUSED_SHIFT;
+    const int cs = fused_cc ? CHUNK_FUSED_SHIFT : 8;
+    eIcicleError er;
+    {
+        ProfScope ps("msm.digits", st);
+        er = psort ? launch_digits_part(scalars, scalars_mont, bases, n, P, S, fused_cc, st)
+                   : launch_digits(scalars, scalars_mont, n, P, S, st);
+        if (er != MBLS_SUCCESS) return er;
+    }
+    ProfScope ps("msm.sort", st);
+    // chunk_off = exclusive scan of the chunk counts, spread over the kernels below: block
+    // prefixes in k_chunk_counts or k_part_sort (written over `counts`, no longer needed), the
+    // block totals scanned beside the order histograms, the sum in k_chunk_owner
+    uint32_t* cloc = S.counts;
+    const uint32_t nblk = (TB + (1u << cs) - 1) >> cs;
+    uint32_t* blk_tot = S.tmp;
+    uint32_t* blk_pre = S.tmp + (nblk + 2);
+    if (psort) {
+        ChunkCountOut cc;
+        if (fused_cc) {
+            cc.nchunks = S.nchunks;
+            cc.binhist = S.binhist;
+            cc.blk_tot = blk_tot;
+            cc.L = P.chunk;
+            cc.m = TB;
+        }
+        if ((er = launch_part_sort(P, S, cc, st)) != MBLS_SUCCESS) return er;
+    } else {
+        if ((er = scan_exclusive(S.counts, S.offsets, TB, S.tmp, st)) != MBLS_SUCCESS) return er;
+        // the maximum and the HeavyTab counters, which the partitioned sort's digit pass clears
+        MBLS_TRY(hipMemsetAsync(S.nchunks + TB, 0, 12, st));
+    }
+    if (!fused_cc)
+        hipLaunchKernelGGL(k_chunk_counts, dim3(blocks), dim3(256), 0, st, S.counts, S.offsets, S.nchunks, TB, P.chunk,
+                           S.binhist, blocks, cloc, blk_tot);
+    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, S.binhist, S.binbase, order_words(TB), blk_tot,
+                       blk_pre, nblk);
+    if (!psort)
+        hipLaunchKernelGGL(k_scatter, dim3((unsigned)((P.contributions + 255) / 256)), dim3(256), 0, st, S.keys, S.vals,
+                           S.ranks, P.contributions, S.offsets, S.sorted);
+    hipLaunchKernelGGL(k_chunk_owner, dim3(blocks), dim3(256), 0, st, cloc, blk_pre, cs, S.chunk_off, S.offsets, TB,
+                       P.chunk, S.owner, S.first, S.nchunks, S.binbase, S.perm, S.H);
     MBLS_TRY(hipGetLastError());
     return MBLS_SUCCESS;
 }

@@ -7,11 +7,12 @@
 //
 // Pipeline (all on the caller's stream; scratch: one region of the leased arena, laid out by
 // msm_scratch below -- the one list of its blocks, used both to size and to carve it):
-//   1-3. sort (msm_common.hip): signed c-bit digits of each scalar (Montgomery -> standard if
-//                     flagged, endomorphism split), contributions (index|sign) sorted by bucket.
-//                     c <= 16 (default): the partitioned counting sort, k_digits_part +
-//                     k_part_sort.  c > 16: k_digits (key, value pairs, bucket histogram by
-//                     atomics), scans, k_scatter.  Then k_chunk_counts / k_chunk_owner: buckets
+//   1-3. the front (msm_front, msm_common.hip; one front serves G1 and G2): signed c-bit digits
+//                     of each scalar (Montgomery -> standard if flagged, endomorphism split with
+//                     its per-call image table), contributions (index|sign) sorted by bucket.
+//                     c <= 16 (default, and every split plan): the partitioned counting sort,
+//                     k_digits_part + k_part_sort.  Unsplit c > 16: k_digits (key, value pairs,
+//                     bucket histogram by atomics), scans, k_scatter.  Then k_chunk_counts / k_chunk_owner: buckets
 //                     are split in chunks of <= P.chunk points so one heavy bucket (e.g.
 //                     all-equal scalars) cannot serialise a thread.
 //   4. k_accumulate_r28 (G1) / k_accumulate_r28p (G2): one thread (lane pair) per chunk, sum of
@@ -146,21 +147,7 @@ eIcicleError plan_levels(MsmPlan& p, int Wl);
 // bits between consecutive multiples in a precomputed table: [P, 2^s P, 2^(2s) P, ...], s = ceil(256 / F)
 int precompute_shift(int F);
 
-// ---- non-templated launchers (msm_common.hip) ----------------------------------------
-// c > 16: digits as (key, value) pairs with global-atomic ranks (k_digits / k_digits_glv)
-eIcicleError launch_digits(const uint8_t* scalars, bool mont, uint32_t n, const MsmPlan& P, uint32_t* keys,
-                           uint32_t* vals, uint32_t* ranks, uint32_t* counts, hipStream_t st);
-size_t digits_src_bytes(uint32_t n, int split);
-eIcicleError scan_exclusive(const uint32_t* in, uint32_t* out, uint32_t m, uint32_t* tmp, hipStream_t st);
-eIcicleError launch_chunk_counts(const uint32_t* counts, const uint32_t* offsets, uint32_t* nchunks, uint32_t m,
-                                 uint32_t L, uint32_t* binhist, uint32_t groups, bool zeroed, uint32_t* cloc,
-                                 uint32_t* blk_tot, hipStream_t st);
-// blk_tot: the chunk-count block totals (nblk of them), scanned into blk_pre
-eIcicleError launch_order_scan(const uint32_t* binhist, uint32_t* binbase, uint32_t m, const uint32_t* blk_tot,
-                               uint32_t* blk_pre, uint32_t nblk, hipStream_t st);
-uint32_t order_words(uint32_t m);
-eIcicleError launch_scatter(const uint32_t* keys, const uint32_t* vals, const uint32_t* ranks, size_t total,
-                            const uint32_t* offsets, uint32_t* sorted, hipStream_t st);
+// ---- the front and the other non-templated stages (msm_common.hip) -------------------
 // heavy buckets (> SMALL_MAX chunk partials), listed by k_chunk_owner for k_bucket_small's slice
 // workgroups.  cnt[0] = heavy buckets, cnt[1] = slices: words TB + 1, TB + 2 of the chunk-count
 // array, zeroed by the digit pass with the chunk-count maximum at TB.
@@ -175,41 +162,6 @@ struct HeavyTab {
     uint32_t* gdone;    // planned slices: group of HEAVY_GROUP slices led by g -> slices finished
 };
 static constexpr uint32_t HEAVY_GDONE = 2048;  // gdone words (zeroed by k_chunk_owner)
-// cloc / blk_pre: the chunk-count prefixes inside blocks of 2^cs buckets and the blocks' scan
-eIcicleError launch_chunk_owner(const uint32_t* cloc, const uint32_t* blk_pre, int cs, uint32_t* chunk_off,
-                                const uint32_t* offsets, uint32_t m, uint32_t L, uint32_t* owner, uint32_t* first,
-                                const uint32_t* nchunks, const uint32_t* binbase, uint32_t* perm, HeavyTab H,
-                                hipStream_t st);
-eIcicleError launch_scalars_from_mont(uint8_t* s, size_t n, hipStream_t st);
-eIcicleError launch_glv_table(const uint8_t* bases, uint8_t* phi, uint32_t n, hipStream_t st);
-// host (pinned: a PCIe-reading copy kernel; pageable: hipMemcpyAsync) or peer memory -> device
-eIcicleError stage_to_device(void* dst, const void* src, size_t bytes, hipStream_t st);
-eIcicleError launch_psi_table(const uint8_t* bases, uint8_t* phi, uint32_t n, hipStream_t st);
-// point-major endomorphism image table (prepared bases): out[S i + j] = endo^j(P_i), S = 2 (G1) / 4 (G2)
-eIcicleError launch_endo_table(const uint8_t* in, uint8_t* out, uint32_t n, int split, hipStream_t st);
-size_t scan_tmp_words(uint32_t m);
-
-// partitioned counting sort (msm_common.hip 2b): pass A digits -> per-segment coarse parts,
-// pass B per-part LDS counting sort.  Replaces keys / vals / ranks + k_scatter for c <= 16.
-struct PartSortSizes {
-    uint32_t NP = 0, tiles = 0, segments = 0;
-    int FB = 0;
-    bool pack = false;
-    size_t ent = 0, segtab = 0, parts = 0;  // bytes
-};
-bool partition_sort(const MsmPlan& P);
-PartSortSizes part_sort_sizes(const MsmPlan& P);
-// bases / phi: the endomorphism table is written by the split kernel itself (k_glv_prep, k_psi_prep)
-// chunk counts computed by the partition sort itself (k_part_sort, parts of 128 fine buckets):
-// k_chunk_counts' outputs with the prefixes in blocks of 128 buckets (CHUNK_FUSED_SHIFT)
-struct ChunkCountOut {
-    uint32_t* nchunks = nullptr;  // null: not fused (k_part_sort writes the bucket counts)
-    uint32_t* binhist = nullptr;  // order histograms (accumulated: zeroed by the digit pass)
-    uint32_t* blk_tot = nullptr;  // per 128-bucket block: the chunk-count total
-    uint32_t L = 0, m = 0;        // chunk length, bucket count
-};
-static constexpr int CHUNK_FUSED_SHIFT = 7;
-bool part_sort_fuses_chunks(const MsmPlan& P);
 // helpers of heavy parts (skewed scalars; msm_common.hip k_part_heavy_count): help[M] per part
 // (first helper << 16 | helpers, 0: light), hh[PH_HELPERS][128] the helpers' fine counts,
 // hpart[PH_HELPERS] each helper's part (~0: idle)
@@ -219,15 +171,42 @@ struct PartHelp {
     uint32_t* hh = nullptr;
     uint32_t* hpart = nullptr;
 };
-// zero2 / nzero2: words the digit pass clears besides its own (the fused order histograms)
-eIcicleError launch_digits_part(const uint8_t* scalars, bool mont, uint32_t n, const MsmPlan& P, uint32_t* ent,
-                                uint32_t* seg_off, uint32_t* seg_cnt, uint32_t* part_tot, uint8_t* dsrc,
-                                uint32_t* zero_word, hipStream_t st, const uint8_t* bases = nullptr,
-                                uint8_t* phi = nullptr, uint32_t* zero2 = nullptr, uint32_t nzero2 = 0);
-// counts: the bucket counts, or with cc.nchunks the chunk-count prefixes (cloc)
-eIcicleError launch_part_sort(const MsmPlan& P, const uint32_t* ent, const uint32_t* seg_off, const uint32_t* seg_cnt,
-                              const uint32_t* part_tot, uint32_t* counts, uint32_t* offsets, uint32_t* sorted,
-                              const ChunkCountOut& cc, hipStream_t st, const PartHelp& hp = PartHelp());
+// the scratch blocks of one MSM, in arena order; msm_scratch below is their one description
+struct MsmScratch {
+    uint32_t *keys, *vals, *ranks;  // atomic-rank sort, c > 16 (zero bytes with the partitioned sort)
+    uint8_t* dsrc;
+    uint32_t *sorted, *counts, *offsets, *nchunks, *chunk_off, *tmp, *owner, *first;
+    uint8_t *partials, *buckets, *levelT, *levelR, *windows;
+    uint8_t* phi;                                  // the per-call image table, or null
+    uint32_t *ent, *seg_off, *seg_cnt, *part_tot;  // partitioned sort (zero bytes with the atomic-rank sort)
+    PartHelp ph;
+    uint32_t *binhist, *binbase, *perm;  // k_bucket_order: bin histograms, their scan, bucket permutation
+    HeavyTab H;
+};
+
+// digits, sort and chunk tables of one MSM on `st`: writes S.sorted, S.offsets, S.chunk_off,
+// S.first, S.owner, S.perm, S.binbase, S.nchunks, S.H and, for a per-call image table, S.phi
+eIcicleError msm_front(const uint8_t* scalars, bool scalars_mont, const uint8_t* bases, uint32_t n,
+                       const MsmPlan& P, const MsmScratch& S, hipStream_t st);
+// what msm_scratch sizes the front's blocks from.  partition_sort: c <= 16 runs the partitioned
+// counting sort (pass A digits -> per-segment coarse parts, pass B per-part LDS counting sort;
+// msm_common.hip 2b) instead of keys / vals / ranks + k_scatter
+struct PartSortSizes {
+    uint32_t NP = 0, tiles = 0, segments = 0;
+    int FB = 0;
+    bool pack = false;
+    size_t ent = 0, segtab = 0, parts = 0;  // bytes
+};
+bool partition_sort(const MsmPlan& P);
+PartSortSizes part_sort_sizes(const MsmPlan& P);
+size_t digits_src_bytes(uint32_t n, int split);
+size_t scan_tmp_words(uint32_t m);
+uint32_t order_words(uint32_t m);
+eIcicleError launch_scalars_from_mont(uint8_t* s, size_t n, hipStream_t st);
+// host (pinned: a PCIe-reading copy kernel; pageable: hipMemcpyAsync) or peer memory -> device
+eIcicleError stage_to_device(void* dst, const void* src, size_t bytes, hipStream_t st);
+// point-major endomorphism image table (prepared bases): out[S i + j] = endo^j(P_i), S = 2 (G1) / 4 (G2)
+eIcicleError launch_endo_table(const uint8_t* in, uint8_t* out, uint32_t n, int split, hipStream_t st);
 
 // ------------------------------------------------------------------------------------
 // 4. accumulation: thread t sums the L contributions at sorted positions [L t, L t + L),
@@ -1497,23 +1476,10 @@ __global__ __launch_bounds__(128) void k_precompute(const uint8_t* in, uint8_t* 
 // ------------------------------------------------------------------------------------
 // host orchestration
 // ------------------------------------------------------------------------------------
-// the scratch blocks of one MSM, in arena order; msm_scratch below is their one description
-struct MsmScratch {
-    uint32_t *keys, *vals, *ranks;  // atomic-rank sort, c > 16 (zero bytes with the partitioned sort)
-    uint8_t* dsrc;
-    uint32_t *sorted, *counts, *offsets, *nchunks, *chunk_off, *tmp, *owner, *first;
-    uint8_t *partials, *buckets, *levelT, *levelR, *windows;
-    uint8_t* phi;                                  // the per-call image table, or null
-    uint32_t *ent, *seg_off, *seg_cnt, *part_tot;  // partitioned sort (zero bytes with the atomic-rank sort)
-    PartHelp ph;
-    uint32_t *binhist, *binbase, *perm;  // k_bucket_order: bin histograms, their scan, bucket permutation
-    HeavyTab H;
-};
-
 // Tuning knobs in this file are compile-time macros for tools/ variant builds (never run-time
 // environment reads: a prover's environment must not select untested kernels).
 
-// the endomorphism images of the bases are built per call (msm_device's `phi` block)
+// the endomorphism images of the bases are built per call (msm_front, into the `phi` block)
 inline bool msm_image_table(const MsmPlan& P) { return P.split > 1 && !P.prepared; }
 // The one description of an MSM's scratch region: every block in arena order, its bytes and the
 // pointer it becomes.  With `base` it carves the region into S; without (the counting pass) S's
@@ -1675,9 +1641,10 @@ struct TailPipe {
 // Core MSM on device operands: scalars (standard or Montgomery), bases Montgomery affine
 // (F*n entries when precomputed); result: one Jacobian Montgomery point on device, or, with
 // icicle_out, ICICLE's normalised (x, y, 1) written there by the final fold's launch.
-// Everything is enqueued on `st`; side streams of the leased context are forked from it and
-// joined back, so the caller sees one stream-ordered operation -- except with `pipe`, where the
-// reduction and the final fold are left on pipe->side for the caller to join.
+// Everything is enqueued on `st`, one stream-ordered operation that creates no stream and no
+// event -- except with `pipe` (the batch pipeline), where the front runs on pipe->front and is
+// joined back before the accumulation, and the reduction and the final fold are left on
+// pipe->side for the caller to join.
 template <class F>
 eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t* bases, uint32_t n,
                         const MsmPlan& P, uint8_t* result, StreamCtx& ctx, hipStream_t st,
@@ -1697,7 +1664,6 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
     }
     const uint32_t TB = P.TB;
     const size_t NC = P.contributions;
-    const bool img_table = msm_image_table(P), psort = partition_sort(P);
     MsmScratch S;
     uint8_t* region = static_cast<uint8_t*>(arena.take(msm_scratch_bytes<F>(P)));
     if (!region) return MBLS_ALLOCATION_FAILED;
@@ -1711,81 +1677,16 @@ eIcicleError msm_device(const uint8_t* scalars, bool scalars_mont, const uint8_t
         if (pipe->front_wait) MBLS_TRY(hipStreamWaitEvent(pipe->front, pipe->front_wait, 0));
         st = pipe->front;
     }
-    // side stream: the endomorphism table overlaps the digit / sort front (fork ev[0], join ev[1])
-    if ((er = ctx.ensure_side(2, 1)) != MBLS_SUCCESS) return er;
-    hipStream_t side = ctx.sides[0];
-    hipEvent_t* ev = ctx.events.data();
-    // with the partitioned sort the endomorphism table is written by the split kernel
-    // (k_glv_prep / k_psi_prep); the atomic-rank sort (c > 16) builds it on the side stream
-    const bool fused_table = img_table && psort;
-    if (img_table && !fused_table) {  // endomorphism images of the bases: phi(P) (G1) or psi^1..3(P) (G2)
-        ctx.forked = true;
-        MBLS_TRY(hipEventRecord(ev[0], st));
-        MBLS_TRY(hipStreamWaitEvent(side, ev[0], 0));
-        er = P.split == 2 ? launch_glv_table(bases, S.phi, n, side) : launch_psi_table(bases, S.phi, n, side);
-        if (er != MBLS_SUCCESS) return er;
-        MBLS_TRY(hipEventRecord(ev[1], side));
-    }
-    // the partition sort of 128-bucket parts also computes the chunk counts (k_chunk_counts'
-    // outputs, prefixes in 128-bucket blocks): one launch fewer
-    const bool fused_cc = psort && part_sort_fuses_chunks(P);
-    const int cs = fused_cc ? CHUNK_FUSED_SHIFT : 8;
-    {
-        ProfScope ps("msm.digits", st);
-        if (psort) {
-            er = launch_digits_part(scalars, scalars_mont, n, P, S.ent, S.seg_off, S.seg_cnt, S.part_tot, S.dsrc,
-                                    S.nchunks + TB, st, fused_table ? bases : nullptr, fused_table ? S.phi : nullptr,
-                                    fused_cc ? S.binhist : nullptr, fused_cc ? order_words(TB) : 0u);
-        } else {
-            MBLS_TRY(hipMemsetAsync(S.counts, 0, (size_t)TB * 4, st));
-            er = launch_digits(scalars, scalars_mont, n, P, S.keys, S.vals, S.ranks, S.counts, st);
-        }
-        if (er != MBLS_SUCCESS) return er;
-    }
-    {
-        ProfScope ps("msm.sort", st);
-        // chunk_off = exclusive scan of the chunk counts, spread over the kernels below: block
-        // prefixes in k_chunk_counts or k_part_sort (written over `counts`, no longer needed), the
-        // block totals scanned beside the order histograms, the sum in k_chunk_owner
-        uint32_t* cloc = S.counts;
-        const uint32_t nblk = (TB + (1u << cs) - 1) >> cs;
-        uint32_t* blk_tot = S.tmp;
-        uint32_t* blk_pre = S.tmp + (nblk + 2);
-        if (psort) {  // writes counts (or with fused_cc the chunk counts), offsets (incl. offsets[TB]) and sorted
-            ChunkCountOut cc;
-            if (fused_cc) {
-                cc.nchunks = S.nchunks;
-                cc.binhist = S.binhist;
-                cc.blk_tot = blk_tot;
-                cc.L = P.chunk;
-                cc.m = TB;
-            }
-            er = launch_part_sort(P, S.ent, S.seg_off, S.seg_cnt, S.part_tot, S.counts, S.offsets, S.sorted, cc, st,
-                                  S.ph);
-            if (er != MBLS_SUCCESS) return er;
-        } else if ((er = scan_exclusive(S.counts, S.offsets, TB, S.tmp, st)) != MBLS_SUCCESS) {
-            return er;
-        }
-        if (!fused_cc && (er = launch_chunk_counts(S.counts, S.offsets, S.nchunks, TB, P.chunk, S.binhist, 1u, psort,
-                                                   cloc, blk_tot, st)) != MBLS_SUCCESS)
-            return er;
-        if ((er = launch_order_scan(S.binhist, S.binbase, TB, blk_tot, blk_pre, nblk, st)) != MBLS_SUCCESS) return er;
-        if (!psort && (er = launch_scatter(S.keys, S.vals, S.ranks, NC, S.offsets, S.sorted, st)) != MBLS_SUCCESS)
-            return er;
-        if ((er = launch_chunk_owner(cloc, blk_pre, cs, S.chunk_off, S.offsets, TB, P.chunk, S.owner, S.first, S.nchunks,
-                                     S.binbase, S.perm, S.H, st)) != MBLS_SUCCESS)
-            return er;
-    }
+    if ((er = msm_front(scalars, scalars_mont, bases, n, P, S, st)) != MBLS_SUCCESS) return er;
     if (st != main_st) {  // join: the accumulation waits for the front
         MBLS_TRY(hipEventRecord(pipe->front_done, st));
         st = main_st;
         MBLS_TRY(hipStreamWaitEvent(st, pipe->front_done, 0));
     }
-    const uint32_t nsplit = img_table ? n : 0xffffffffu;
+    const uint32_t nsplit = msm_image_table(P) ? n : 0xffffffffu;
     {
         // the chunk count is data dependent: launch the bound, extra threads exit
         ProfScope ps("msm.accumulate", st);
-        if (img_table && !fused_table) MBLS_TRY(hipStreamWaitEvent(st, ev[1], 0));
         const uint32_t threads = (uint32_t)((NC + P.chunk - 1) / P.chunk) * LN;
         // bstride > 1: the split kernel wrote [P; phi P] into `phi` (compact slot-0 copy)
         const uint8_t* acc_b = P.bstride > 1 ? S.phi : bases;
@@ -1985,11 +1886,12 @@ eIcicleError msm_call(const void* scalars, const void* bases, int msm_size, cons
                           ? (uint8_t*)results
                           : nullptr;
     const size_t mark = A.mark();
-    // events: 2-3 bucket_done, 4-5 tail done, 6-7 front done, 8 the fork (per region where paired)
-    if (piped && (er = ctx.ensure_side(9, 3)) != MBLS_SUCCESS) return er;
+    // side streams: 0 the tails, 1 the fronts; events: 0-1 bucket_done, 2-3 tail done, 4-5 front
+    // done, 6 the fork (per region where paired)
+    if (piped && (er = ctx.ensure_side(7, 2)) != MBLS_SUCCESS) return er;
     if (piped) {
         ctx.forked = true;
-        MBLS_TRY(hipEventRecord(ctx.events[8], st));
+        MBLS_TRY(hipEventRecord(ctx.events[6], st));
     }
     for (int b = 0; b < batch; ++b) {
         // scratch reused across the batch (stream-ordered); piped: two regions, alternating
@@ -1997,12 +1899,12 @@ eIcicleError msm_call(const void* scalars, const void* bases, int msm_size, cons
         TailPipe pipe;
         if (piped) {
             if ((b & 1) && !A.take(scratch)) return MBLS_ALLOCATION_FAILED;
-            pipe.side = ctx.sides[1];
-            pipe.bucket_done = ctx.events[2 + (b & 1)];
-            pipe.reuse = b >= 2 ? ctx.events[4 + (b & 1)] : nullptr;
-            pipe.front = batch_pipe() > 1 ? ctx.sides[2] : nullptr;
-            pipe.front_wait = b >= 2 ? ctx.events[2 + (b & 1)] : ctx.events[8];
-            pipe.front_done = ctx.events[6 + (b & 1)];
+            pipe.side = ctx.sides[0];
+            pipe.bucket_done = ctx.events[b & 1];
+            pipe.reuse = b >= 2 ? ctx.events[2 + (b & 1)] : nullptr;
+            pipe.front = batch_pipe() > 1 ? ctx.sides[1] : nullptr;
+            pipe.front_wait = b >= 2 ? ctx.events[b & 1] : ctx.events[6];
+            pipe.front_done = ctx.events[4 + (b & 1)];
         }
         const uint8_t* sb = d_s + (size_t)b * n * 32;
         const uint8_t* bb = d_b + (shared ? 0 : (size_t)b * nbases_per * AFF);
@@ -2011,12 +1913,12 @@ eIcicleError msm_call(const void* scalars, const void* bases, int msm_size, cons
         er = msm_device<F>(sb, scal_mont, bb, (uint32_t)n, P, d_r + (size_t)b * JAC, ctx, st, icicle_b,
                            piped ? &pipe : nullptr, b == batch - 1 ? acc_ev.release() : nullptr);
         if (er != MBLS_SUCCESS) return er;
-        if (piped) MBLS_TRY(hipEventRecord(ctx.events[4 + (b & 1)], pipe.side));
+        if (piped) MBLS_TRY(hipEventRecord(ctx.events[2 + (b & 1)], pipe.side));
     }
     // the side stream runs the tails in member order: its last event covers them all
-    if (piped) MBLS_TRY(hipStreamWaitEvent(st, ctx.events[4 + ((batch - 1) & 1)], 0));
-    // every side stream is joined into `st` by now (the table's ev[1] before the accumulation,
-    // the fronts' front_done, the tails' last event above): only an early error return leaves
+    if (piped) MBLS_TRY(hipStreamWaitEvent(st, ctx.events[2 + ((batch - 1) & 1)], 0));
+    // every side stream is joined into `st` by now (the fronts' front_done, the tails' last
+    // event above): only an early error return leaves
     // the lease's fallback join to do
     ctx.forked = false;
     if (!direct) {

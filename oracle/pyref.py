@@ -365,7 +365,7 @@ def msm_precomputed(scalars, points, factor: int, c: int, group: str = "g1"):
 
 
 # --------------------------------------------------------------------------------------
-# GLV split used by the G1 MSM kernel (k_digits_glv).  Not a reference algorithm: the
+# GLV split used by the G1 MSM's split kernels (k_glv_split, k_glv_prep).  Not a reference algorithm: the
 # reference ships GLV constants only behind an experimental flag, off the MSM path
 # (bls12-381/src/curve/point_ops.cu:103-145); the MSM result is unchanged by the split.
 # r = lam^2 + lam + 1 exactly (lam = z^2 - 1), phi(x, y) = (beta x, y) = lam * P on G1.

@@ -161,6 +161,15 @@ def test_reduce_schedule_structure(amd, group, c):
         assert sched["level_bytes"] == (xyzz if stored_raw else jac), (case, sched)
 
 
+def test_split_plans_stay_on_the_partitioned_sort(amd):
+    """a split plan never has c > 16: the GLV / psi digit sources and the per-call image tables
+    exist only on the partitioned sort (msm_front), and make_plan rejects a plan that would leave it"""
+    for group in ("g1", "g2"):
+        for c in GRID_C:
+            for case, p, _ in _grid(amd, group, c):
+                assert p["split"] == 1 or p["c"] <= 16, (group, case, p)
+
+
 def test_reduce_schedule_grid_reaches_every_kind(amd):
     import reduce_tree_model as T
     seen = set()
