@@ -581,6 +581,22 @@ eIcicleError mbls_msm_plan(int group, int msm_size, const MSMConfig* config, int
 eIcicleError mbls_msm_reduce_plan(int group, int msm_size, const MSMConfig* config, int32_t* out, int capacity,
                                   int32_t* count);
 
+/* The tables the MSM's front (digits, sort, chunk tables: msm_front) hands the accumulation and the
+ * bucket sums, for one MSM of msm_size > 0 points under `config` (batch_size 1, the ICICLE entry's
+ * flags).  The call does what an MSM does up to the front -- the same plan, chunk length, operand
+ * staging and scratch region of the stream's leased arena --, fills the region with the byte 0xA5,
+ * runs the front and copies table k out at the full capacity of its scratch block.
+ * info[0..14] = c, W, Wg, F, sF, split, prepared, bstride, buckets per window B, buckets TB, chunk
+ * length, point indices, contributions, partitioned sort (0 / 1), fused chunk counts (0 / 1);
+ * info[15 + k] = the 32-bit words of table k: 0 sorted, 1 offsets, 2 nchunks (word TB the maximum,
+ * TB + 1 the heavy buckets, TB + 2 their slices), 3 chunk_off, 4 owner, 5 first, 6 perm, 7 binbase,
+ * 8..12 the heavy-bucket table's bucket, first, nslices, done, owner, 13 its group counters.
+ * tables == NULL: only `info` is written, no device work.  Otherwise tables[k] is a host buffer of
+ * info[15 + k] words, or NULL to leave table k out.  `bases` may be NULL for every plan without a
+ * per-call image table (info[5] == 1 or info[6] == 1).  Diagnostics (tests/test_gpu_front.py). */
+eIcicleError mbls_msm_front_probe(int group, const mbls_fr_t* scalars, const void* bases, int msm_size,
+                                  const MSMConfig* config, int64_t* info, void* const* tables);
+
 /* Stage profiler (tracing): hipEvent pairs recorded on the caller's
  * stream around each pipeline stage ("msm.accumulate", "ntt.pass", ...) when enabled
  * (or MBLS_PROFILE=1).  read() synchronises the recorded events and returns, per stage,

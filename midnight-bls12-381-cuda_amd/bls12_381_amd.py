@@ -77,7 +77,7 @@ EXPORTED = [
     "mbls_release_stream", "mbls_release_scratch", "mbls_scratch_stats",
     "mbls_g1_msm_multi_device", "mbls_g2_msm_multi_device", "bls12_381_vector_sum",
     "bls12_381_g1_affine_to_projective", "bls12_381_g1_projective_to_affine", "bls12_381_g2_projective_to_affine",
-    "mbls_msm_plan", "mbls_msm_reduce_plan", "mbls_msm_accumulate_event", "mbls_msm_accumulate_event_drop", "mbls_msm_precompute_strict",
+    "mbls_msm_plan", "mbls_msm_reduce_plan", "mbls_msm_front_probe", "mbls_msm_accumulate_event", "mbls_msm_accumulate_event_drop", "mbls_msm_precompute_strict",
     "bls12_381_g1_scalar_mul", "bls12_381_g1_scalar_mul_glv", "bls12_381_g2_scalar_mul",
     "mbls_g1_scalar_mul", "mbls_g2_scalar_mul", "mbls_g1_ecntt",
     "mbls_g1_check_points", "mbls_g2_check_points",
@@ -127,6 +127,7 @@ def lib():
         "bls12_381_g1_affine_to_projective": [P, i32, P, P], "bls12_381_g1_projective_to_affine": [P, i32, P, P],
         "bls12_381_g2_projective_to_affine": [P, i32, P, P],
         "mbls_msm_plan": [i32, i32, P, P], "mbls_msm_reduce_plan": [i32, i32, P, P, i32, P],
+        "mbls_msm_front_probe": [i32, P, P, i32, P, P, P],
         "mbls_msm_accumulate_event": [P, P], "mbls_msm_accumulate_event_drop": [P],
         "mbls_msm_precompute_strict": [i32],
         "bls12_381_g1_scalar_mul": [P, P, i32, P, P], "bls12_381_g1_scalar_mul_glv": [P, P, i32, P, P],
@@ -250,6 +251,47 @@ def msm_reduce_plan(group, n, **cfg):
         lv["kernel"], lv["mode"] = REDUCE_KERNELS[lv["kernel"]], REDUCE_MODES[lv["mode"]]
         levels.append(lv)
     return dict(bucket_raw=out[0], level_bytes=out[1], levels=levels)
+
+
+FRONT_PLAN_FIELDS = ("c", "W", "Wg", "F", "sF", "split", "prepared", "bstride", "B", "TB", "chunk", "pts",
+                     "contributions", "partition_sort", "fused_chunk_counts")
+FRONT_TABLES = ("sorted", "offsets", "nchunks", "chunk_off", "owner", "first", "perm", "binbase", "H_bucket",
+                "H_first", "H_nslices", "H_done", "H_owner", "H_gdone")
+FRONT_FILL = 0xA5A5A5A5  # a word of a scratch block the front did not write
+
+
+def msm_front_plan(group, n, **cfg):
+    """the plan msm_front_tables(group, <n scalars>, **cfg) runs and its tables' capacities in words
+    (mbls_msm_front_probe without tables; host only): dict(plan, words)"""
+    c = msm_config(**cfg)
+    info = (ctypes.c_int64 * (len(FRONT_PLAN_FIELDS) + len(FRONT_TABLES)))()
+    check(lib().mbls_msm_front_probe(1 if group == "g1" else 2, None, None, n, ctypes.byref(c), info, None),
+          "msm_front_probe")
+    k = len(FRONT_PLAN_FIELDS)
+    return dict(plan=dict(zip(FRONT_PLAN_FIELDS, list(info)[:k])), words=dict(zip(FRONT_TABLES, list(info)[k:])))
+
+
+def msm_front_tables(group, scalars, bases=None, *, n=None, c=0, bitsize=0, precompute_factor=1, scalars_mont=False,
+                     points_mont=True, stream=None):
+    """The front's tables of the MSM msm(group, scalars, bases, ...) would run (mbls_msm_front_probe):
+    dict(plan = dict of FRONT_PLAN_FIELDS as the call used them, tables = dict of FRONT_TABLES, each a
+    uint32 numpy array of its scratch block's full capacity, words the front left alone holding
+    FRONT_FILL).  scalars (n, 4) uint64, numpy (host) or torch (device); bases may be None where the
+    plan builds no per-call image table."""
+    if n is None:
+        n = scalars.shape[0]
+    cfg = msm_config(c=c, bitsize=bitsize, precompute_factor=precompute_factor,
+                     are_scalars_on_device=_is_dev(scalars), are_scalars_montgomery_form=scalars_mont,
+                     are_points_on_device=_is_dev(bases), are_points_montgomery_form=points_mont, stream=stream)
+    g = 1 if group == "g1" else 2
+    info = (ctypes.c_int64 * (len(FRONT_PLAN_FIELDS) + len(FRONT_TABLES)))()
+    check(lib().mbls_msm_front_probe(g, None, None, n, ctypes.byref(cfg), info, None), "msm_front_probe")
+    words = list(info)[len(FRONT_PLAN_FIELDS):]
+    tabs = [np.zeros(w, dtype=np.uint32) for w in words]
+    ptrs = (ctypes.c_void_p * len(tabs))(*[t.ctypes.data for t in tabs])
+    check(lib().mbls_msm_front_probe(g, _p(scalars), _p(bases), n, ctypes.byref(cfg), info, ptrs), "msm_front_probe")
+    assert list(info)[len(FRONT_PLAN_FIELDS):] == words
+    return dict(plan=dict(zip(FRONT_PLAN_FIELDS, list(info))), tables=dict(zip(FRONT_TABLES, tabs)))
 
 
 def ntt_config(**kw):

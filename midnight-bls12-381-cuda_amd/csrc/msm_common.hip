@@ -1876,3 +1876,129 @@ eIcicleError multi_device_res(int dev, MultiDevRes*& out) {
 }
 
 }  // namespace mbls
+
+// ------------------------------------------------------------------------------------
+// diagnostics: the front's tables of one MSM (mbls_msm_front_probe, tests/test_gpu_front.py)
+// ------------------------------------------------------------------------------------
+namespace mbls {
+
+static constexpr int FRONT_PLAN_WORDS = 15, FRONT_TABLES = 14;
+
+// msm_call up to the front (plan, chunk length, operand staging, scratch carved from the leased
+// arena), then the region filled with 0xA5, msm_front, and every table copied out at the capacity
+// msm_scratch gave its block (the bytes up to the next block).  tables == null: the plan and the
+// capacities only, no device work.
+template <class F>
+static eIcicleError front_probe(const void* scalars, const void* bases, int msm_size, const MSMConfig* cfg,
+                                int64_t* info, void* const* tables) {
+    constexpr size_t AFF = PointSize<F>::AFF, JAC = PointSize<F>::JAC;
+    if (!cfg || !info) return MBLS_INVALID_POINTER;
+    if (msm_size <= 0 || msm_size > (1 << MAX_MSM_LOG) || cfg->batch_size > 1) return MBLS_INVALID_ARGUMENT;
+    if (tables && !scalars) return MBLS_INVALID_POINTER;
+    hipStream_t st = static_cast<hipStream_t>(cfg->stream);
+    MSMConfig cfg_plain;
+    if (cfg->precompute_factor > 1 && cfg->are_points_on_device && bases) {  // msm_call's table guard
+        const size_t want = (size_t)msm_size * (size_t)cfg->precompute_factor * AFF;
+        if (precompute_strict() ? !precompute_is_table(bases, cfg->precompute_factor, want)
+                                : device_bytes_from(bases) < want) {
+            cfg_plain = *cfg;
+            cfg_plain.precompute_factor = 1;
+            cfg = &cfg_plain;
+        }
+    }
+    MsmPlan P;
+    eIcicleError er = make_plan(msm_size, cfg, P, std::is_same<F, Fq>::value ? 2 : 4);
+    if (er != MBLS_SUCCESS) return er;
+    P.chunk = accumulate_chunk<F>(P);
+    const bool psort = partition_sort(P);
+    const int64_t plan[FRONT_PLAN_WORDS] = {P.c, P.W, P.Wg, P.F, P.sF, P.split, P.prepared ? 1 : 0, P.bstride,
+                                            (int64_t)P.B, (int64_t)P.TB, (int64_t)P.chunk, (int64_t)P.pts,
+                                            (int64_t)P.contributions, psort ? 1 : 0,
+                                            psort && part_fine_bits(P.B) == CHUNK_FUSED_SHIFT ? 1 : 0};
+    for (int k = 0; k < FRONT_PLAN_WORDS; ++k) info[k] = plan[k];
+    const size_t scratch = msm_scratch_bytes<F>(P);
+    // each table with the block behind it in msm_scratch's order
+    auto blocks = [&](const MsmScratch& S, uint8_t* region, const uint8_t* (&lo)[FRONT_TABLES],
+                      const uint8_t* (&hi)[FRONT_TABLES]) {
+        const void* t[FRONT_TABLES][2] = {
+            {S.sorted, S.counts},     {S.offsets, S.nchunks},     {S.nchunks, S.chunk_off}, {S.chunk_off, S.tmp},
+            {S.owner, S.first},       {S.first, S.partials},      {S.perm, S.H.bucket},     {S.binbase, S.perm},
+            {S.H.bucket, S.H.first},  {S.H.first, S.H.nslices},   {S.H.nslices, S.H.done},  {S.H.done, S.H.owner},
+            {S.H.owner, S.H.res},     {S.H.gdone, region + scratch}};
+        for (int k = 0; k < FRONT_TABLES; ++k) {
+            lo[k] = static_cast<const uint8_t*>(t[k][0]);
+            hi[k] = static_cast<const uint8_t*>(t[k][1]);
+        }
+    };
+    const uint8_t *lo[FRONT_TABLES], *hi[FRONT_TABLES];
+    MsmScratch S;
+    if (!tables) {  // the layout alone, over an address that is never read
+        uint8_t* nowhere = reinterpret_cast<uint8_t*>(uintptr_t(1) << 30);
+        msm_scratch<F>(P, nowhere, S);
+        blocks(S, nowhere, lo, hi);
+        for (int k = 0; k < FRONT_TABLES; ++k) info[FRONT_PLAN_WORDS + k] = (int64_t)((hi[k] - lo[k]) / 4);
+        return MBLS_SUCCESS;
+    }
+    if (msm_image_table(P) && !bases) return MBLS_INVALID_POINTER;  // the front reads them for S.phi only
+
+    const bool scal_mont = cfg->are_scalars_montgomery_form;
+    const bool pts_mont = P.table == 1 ? cfg->are_points_montgomery_form : true;
+    const size_t n = (size_t)msm_size, nbases = n * (size_t)P.table;
+    CtxLease lease(st);
+    if (!lease) return lease.error();
+    StreamCtx& ctx = *lease;
+    Arena& A = ctx.arena;
+    const size_t st_s = !cfg->are_scalars_on_device ? align_up(n * 32) : 0;
+    const size_t st_b = bases && (!cfg->are_points_on_device || !pts_mont) ? align_up(nbases * AFF) : 0;
+    er = lease.reserve(st_s + st_b + align_up(JAC) + scratch + 4096);
+    if (er != MBLS_SUCCESS) return er;
+    const uint8_t* d_s = static_cast<const uint8_t*>(scalars);
+    const uint8_t* d_b = static_cast<const uint8_t*>(bases);
+    if (st_s) {
+        const bool read_once = P.split > 1 || scal_mont;
+        const void* alias = read_once ? pinned_host_device_pointer(scalars) : nullptr;
+        if (alias) {
+            d_s = static_cast<const uint8_t*>(alias);
+        } else {
+            void* t = A.take(n * 32);
+            if ((er = stage_to_device(t, scalars, n * 32, st)) != MBLS_SUCCESS) return er;
+            d_s = static_cast<const uint8_t*>(t);
+        }
+    }
+    if (st_b) {
+        void* t = A.take(nbases * AFF);
+        if (cfg->are_points_on_device) {
+            MBLS_TRY(hipMemcpyAsync(t, bases, nbases * AFF, hipMemcpyDefault, st));
+        } else if ((er = stage_to_device(t, bases, nbases * AFF, st)) != MBLS_SUCCESS) {
+            return er;
+        }
+        if (!pts_mont) {
+            hipLaunchKernelGGL(k_points_to_mont<F>, dim3((unsigned)((nbases + 255) / 256)), dim3(256), 0, st,
+                               (uint8_t*)t, nbases);
+            MBLS_TRY(hipGetLastError());
+        }
+        d_b = static_cast<const uint8_t*>(t);
+    }
+    (void)A.take(JAC);  // msm_call's result slot
+    uint8_t* region = static_cast<uint8_t*>(A.take(scratch));
+    if (!region) return MBLS_ALLOCATION_FAILED;
+    msm_scratch<F>(P, region, S);
+    blocks(S, region, lo, hi);
+    MBLS_TRY(hipMemsetAsync(region, 0xA5, scratch, st));
+    if ((er = msm_front(d_s, scal_mont, d_b, (uint32_t)n, P, S, st)) != MBLS_SUCCESS) return er;
+    MBLS_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < FRONT_TABLES; ++k) {
+        info[FRONT_PLAN_WORDS + k] = (int64_t)((hi[k] - lo[k]) / 4);
+        if (tables[k]) MBLS_TRY(hipMemcpy(tables[k], lo[k], (size_t)(hi[k] - lo[k]), hipMemcpyDeviceToHost));
+    }
+    return MBLS_SUCCESS;
+}
+
+}  // namespace mbls
+
+extern "C" eIcicleError mbls_msm_front_probe(int group, const mbls_fr_t* scalars, const void* bases, int msm_size,
+                                             const MSMConfig* config, int64_t* info, void* const* tables) {
+    if (group == 1) return mbls::front_probe<Fq>(scalars, bases, msm_size, config, info, tables);
+    if (group == 2) return mbls::front_probe<Fq2>(scalars, bases, msm_size, config, info, tables);
+    return MBLS_INVALID_ARGUMENT;
+}

@@ -953,10 +953,12 @@ def _skewed(case, n, g):
                                               ("g1", 22, "ones"), ("g2", 14, "ones"), ("g2", 14, "bits8"),
                                               ("g2", 14, "repeated"), ("g2", 16, "repeated"), ("g2", 16, "half_one")])
 def test_msm_skewed_scalars(amd, gh, group, log_n, case):
-    """skewed scalar distributions put most contributions into a few buckets (heavy parts of the
-    partitioned sort and their helper workgroups -- parts above 2^15 entries: G1 2^20, G2 2^16 --,
-    long owner ranges, heavy bucket slices: planned and grouped, or the fixed plan past 1024 heavy
-    buckets with `few_values`) -- equal to the oracle"""
+    """skewed scalar distributions put most contributions into a few buckets (long owner ranges,
+    heavy bucket slices: planned and grouped, or the fixed plan past 1024 heavy buckets with
+    `few_values`; heavy parts of the partitioned sort with their helper workgroups only at G1 2^20 and
+    above and G2 2^16: a part is heavy ABOVE PH_MIN = 2^15 entries, and the G1 2^15 / G2 2^14 cases
+    put at most exactly 2^15 into one part, which stays light -- tests/test_gpu_front.py brackets
+    that comparison) -- equal to the oracle"""
     import torch
     n = 1 << log_n
     w = 12 if group == "g1" else 24
