@@ -260,6 +260,61 @@ eIcicleError mbls_fr_poly_divide_linear(const mbls_fr_t* coeffs, size_t size, co
 eIcicleError mbls_fr_scan_geometry(size_t size, int32_t* out);
 
 /* ------------------------------------------------------------------------------------ */
+/* Fr column sort, and the lookup argument's permuted pair on top of it (step 2 of a halo2-style
+ * lookup_prover: permute_expression_pair, between the theta-compression -- mbls_fr_eval_program --
+ * and the commitments and grand product -- the MSM and mbls_fr_prefix_product).  (No reference
+ * counterpart: the reference sorts on the CPU and uploads the Permuted columns afterwards.)
+ *   elements: 32 bytes, canonical (< r), Montgomery when `montgomery` is set, else standard form.
+ *     Outputs are the input elements themselves, moved, byte for byte: nothing is converted.
+ *   order: ascending by the element's standard-form integer value -- what Ord gives on the
+ *     blst-backed scalar type.  This is this library's definition (the reference tree holds none); a
+ *     proof is valid under any total order, the order matters only for reproducing a CPU transcript.
+ *     With `montgomery` set the key is still the standard value, from_mont(x), not the stored words.
+ *     A non-canonical element has an unspecified position; it never causes an out-of-range access.
+ *   batch: config->batch_size members (0 counts as 1), row-major, each of `size` elements, sorted
+ *     independently.  columns_batch gives API_NOT_IMPLEMENTED, as the scans do.
+ *   placement: config->is_a_on_device input and table (both alike), is_result_on_device the vector
+ *     outputs.  Host buffers are staged through the leased scratch context, which also holds every
+ *     work array (no allocation per call once it is large enough; mbls_fr_sort_plan reports the
+ *     bytes); a host output makes the call synchronous, otherwise it synchronises unless is_async.
+ *   errors, before any device work: INVALID_POINTER for a null input, table, config or a missing
+ *     required output; INVALID_ARGUMENT for size == 0 or size * batch > 2^26.
+ *   overlap: outputs must not overlap inputs; undefined.
+ *   timing: NOT constant time.  Digit bins, the skipping of key words that are the same in every
+ *     element, and the lookup's binary search depend on the values, as the MSM's bucket sort over
+ *     witness scalars does.                                                                      */
+/* ------------------------------------------------------------------------------------ */
+/* sorted[k*size + i] = the i-th smallest element of member k; perm[k*size + i] = its index within
+ * member k.  Equal elements come in ascending original index (the sort is stable).  Either of
+ * sorted and perm may be NULL, not both. */
+eIcicleError mbls_fr_sort(const mbls_fr_t* input, size_t size, bool montgomery, const VecOpsConfig* config,
+                          mbls_fr_t* sorted, uint32_t* perm);
+/* Per member, over size = the caller's usable rows (the caller writes the blinding rows after them):
+ *   permuted_input = A' = the sorted input; T = the sorted table.
+ *   A row of A' is FIRST when it is row 0 or differs from the row above it, else REPEATED.
+ *   For every first row with value v: if v occurs in T, the first occurrence of v in T is consumed;
+ *   otherwise v is missing.  L = the unconsumed entries of T, ascending; R_0 < .. < R_{m-1} = the
+ *   repeated rows.
+ *   permuted_table[i] = A'[i] on first rows, permuted_table[R_q] = L[m-1-q] on repeated rows.
+ * This is permute_expression_pair exactly: its ordered map is walked in ascending order and the
+ * repeated rows are popped from the back.  Both vector outputs are required.
+ * n_missing: a HOST pointer to `batch` counts, n_missing[k] = the distinct input values of member k
+ * that its table lacks; may be NULL; non-NULL makes the call synchronous.  A member with missing
+ * values is data, not an error (SUCCESS): its outputs are still the formulas' (L then has at least m
+ * entries), and the caller must treat it as a failed lookup (the CPU's ConstraintSystemFailure). */
+eIcicleError mbls_fr_lookup_permute(const mbls_fr_t* input, const mbls_fr_t* table, size_t size, bool montgomery,
+                                    const VecOpsConfig* config, mbls_fr_t* permuted_input,
+                                    mbls_fr_t* permuted_table, uint64_t* n_missing);
+/* host only, no device work.  For size in 1..2^26 and batch >= 1 with size * batch <= 2^26:
+ * out[0] = bits per digit, out[1] = digit passes of mbls_fr_sort when no key word is skipped (the
+ * key's, plus those over the member number for batch > 1), out[2] = elements per workgroup tile,
+ * out[3] = workgroups per pass of mbls_fr_sort (all members together: they ride in one array),
+ * out[4] = scratch bytes of mbls_fr_sort, out[5] = scratch bytes of mbls_fr_lookup_permute (staging
+ * of host operands not counted).  A workgroup takes a whole number of tiles; the lookup sorts
+ * 2 * size * batch elements and scans 2 * size * batch + 1 rank words with the same tile. */
+eIcicleError mbls_fr_sort_plan(size_t size, int batch, int64_t* out);
+
+/* ------------------------------------------------------------------------------------ */
 /* Fr expression evaluator: one caller-supplied straight-line stack program run once per row over
  * a set of columns read at rotated rows -- the permutation numerators and denominators that feed
  * mbls_fr_prefix_product, the theta-compression of lookup columns, the gate / permutation / lookup

@@ -84,6 +84,7 @@ EXPORTED = [
     "mbls_g1_decompress", "mbls_g2_decompress", "mbls_g1_compress", "mbls_g2_compress",
     "mbls_fr_prefix_product", "mbls_fr_poly_divide_linear", "mbls_fr_scan_geometry",
     "mbls_fr_eval_program", "mbls_fr_expr_check",
+    "mbls_fr_sort", "mbls_fr_lookup_permute", "mbls_fr_sort_plan",
 ]
 
 _LIB = None
@@ -141,6 +142,8 @@ def lib():
         "mbls_fr_scan_geometry": [sz, P],
         "mbls_fr_eval_program": [P, i32, sz, sz, P, i32, P, i32, i32, P, P],
         "mbls_fr_expr_check": [P, i32, i32, i32, i32, P],
+        "mbls_fr_sort": [P, sz, b, P, P, P], "mbls_fr_lookup_permute": [P, P, sz, b, P, P, P, P],
+        "mbls_fr_sort_plan": [sz, i32, P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -534,6 +537,70 @@ def poly_divide_linear(coeffs, z, *, batch=1, out=None, quotient=True, eval=True
     check(lib().mbls_fr_poly_divide_linear(_p(coeffs), n, _p(z), ctypes.byref(cfg), _p(out), _p(eval)),
           "mbls_fr_poly_divide_linear")
     return out, eval
+
+
+# ----------------------------------------------------------------------------- sort and lookup
+SORT_PLAN_FIELDS = ("bits", "passes", "tile", "groups", "sort_bytes", "lookup_bytes")
+
+
+def sort_plan(n, batch=1):
+    """the geometry and scratch of fr_sort / lookup_permute for `batch` members of n elements
+    (mbls_fr_sort_plan; host only): dict of SORT_PLAN_FIELDS -- bits per digit, digit passes when no
+    key word is skipped, elements per workgroup tile, workgroups per pass, scratch bytes of the sort
+    and of the lookup"""
+    out = (ctypes.c_int64 * len(SORT_PLAN_FIELDS))()
+    check(lib().mbls_fr_sort_plan(n, batch, out), "mbls_fr_sort_plan")
+    return dict(zip(SORT_PLAN_FIELDS, list(out)))
+
+
+def _u32_like(ref, rows):
+    if _is_dev(ref):
+        import torch
+        return torch.zeros((rows,), dtype=torch.int32, device=ref.device)
+    return np.zeros(rows, dtype=np.uint32)
+
+
+def fr_sort(x, *, mont=True, batch=1, perm=False, out=None, stream=None, is_async=False):
+    """Stable sort by standard-form value (mbls_fr_sort): x (batch*n, 4) uint64, Montgomery unless
+    mont is False, numpy (host) or torch (device); each of the `batch` members is sorted on its own.
+    Returns the sorted elements (x's own, moved): `out` when given, else placed as x is; out=False
+    asks for none.  With perm=True, or a (batch*n,) uint32 numpy / int32 torch buffer placed as
+    `out`, returns (sorted, perm), perm[k*n + i] = the index within member k of its i-th smallest
+    element, equal elements in ascending index."""
+    n = x.shape[0] // batch
+    if out is None:
+        out = _like(x, x.shape[0])
+    elif out is False:
+        out = None
+    if perm is True:
+        perm = _u32_like(out if out is not None else x, x.shape[0])
+    elif perm is False:
+        perm = None
+    assert out is None or perm is None or _is_dev(out) == _is_dev(perm), "sorted and perm share one placement"
+    cfg = vec_config(is_a_on_device=_is_dev(x), is_result_on_device=_is_dev(out if out is not None else perm),
+                     is_async=is_async, stream=stream, batch_size=batch)
+    check(lib().mbls_fr_sort(_p(x), n, bool(mont), ctypes.byref(cfg), _p(out), _p(perm)), "mbls_fr_sort")
+    return out if perm is None else (out, perm)
+
+
+def lookup_permute(input, table, *, mont=True, batch=1, count=True, out=None, stream=None, is_async=False):
+    """The lookup argument's permuted pair (mbls_fr_lookup_permute): input, table (batch*n, 4) uint64,
+    Montgomery unless mont is False, both numpy (host) or both torch (device).  Returns
+    (permuted_input, permuted_table, n_missing): A' = the sorted input and S' = the table laid out
+    beside it as permute_expression_pair does, `out` = (A', S') buffers when given, else placed as
+    the input is; n_missing a list of `batch` counts of distinct input values absent from the table
+    (any non-zero: a failed lookup), or None for count=False (then device outputs with is_async do
+    not wait)."""
+    n = input.shape[0] // batch
+    assert table.shape[0] == input.shape[0] and _is_dev(table) == _is_dev(input), "input and table share size and placement"
+    pin, ptab = out if out is not None else (_like(input, input.shape[0]), _like(input, input.shape[0]))
+    assert _is_dev(pin) == _is_dev(ptab), "the outputs share one placement"
+    cnt = (ctypes.c_uint64 * batch)() if count else None
+    cfg = vec_config(is_a_on_device=_is_dev(input), is_result_on_device=_is_dev(pin), is_async=is_async, stream=stream,
+                     batch_size=batch)
+    check(lib().mbls_fr_lookup_permute(_p(input), _p(table), n, bool(mont), ctypes.byref(cfg), _p(pin), _p(ptab), cnt),
+          "mbls_fr_lookup_permute")
+    return pin, ptab, ([int(v) for v in cnt] if count else None)
 
 
 # ----------------------------------------------------------------------------- expression evaluator
