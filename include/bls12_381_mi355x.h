@@ -260,6 +260,60 @@ eIcicleError mbls_fr_poly_divide_linear(const mbls_fr_t* coeffs, size_t size, co
 eIcicleError mbls_fr_scan_geometry(size_t size, int32_t* out);
 
 /* ------------------------------------------------------------------------------------ */
+/* Extended-coset transforms: the EvaluationDomain steps of a halo2-style prover, coeff_to_extended
+ * (zero-pad a polynomial of n = 2^k coefficients to N = 2^extended_k and evaluate it on the coset
+ * g * H_N) and extended_to_coeff (divide by the vanishing polynomial, interpolate, undo the coset,
+ * truncate).  The padding, the coset powers, the vanishing division, the N^-1 scaling and the
+ * truncation ride in the first and last passes of the transform, and the forward transform skips
+ * the butterfly stages whose second input is a padding zero.  The NTT entries above are unchanged.
+ * (No reference counterpart: the reference composes these from a coset NTT and CPU passes.)
+ *   elements: Montgomery and canonical (< r), in and out, as for the NTT; every output is canonical.
+ *   sizes: extended_size a power of two, 1 .. 2^30 and within the initialised domain's order, as
+ *     bls12_381_ntt_cuda; size and out_size any value in 1..extended_size, not only powers of two;
+ *     period a power of two <= extended_size (halo2's t_evaluations: 2^(extended_k - k) entries).
+ *     The forward pruning uses E = log2(extended_size / next_pow2(size)).
+ *   coset generator: coset_gen is ONE Montgomery element in HOST memory; NULL or Montgomery one
+ *     means no coset, zero mod r gives INVALID_ARGUMENT as in the NTT.  config->coset_gen is not
+ *     read.  The same g goes into both calls: the inverse derives g^-1 itself.  The library keeps
+ *     the power tables of the last 8 (generator, size, direction) triples with the domain
+ *     (bls12_381_ntt_release_domain_cuda frees them); the first call with a new triple builds its
+ *     tables and waits for them.
+ *   config: stream, batch_size (0 counts as 1; members row-major, `size` / `extended_size` elements
+ *     apart on the input side and `extended_size` / `out_size` apart on the output side),
+ *     are_inputs_on_device, are_outputs_on_device and is_async as in the NTT.  vanishing_inv is
+ *     placed like the input and shared by every member.  columns_batch, or an ordering other than
+ *     kNN, gives INVALID_ARGUMENT (mbls_g1_ecntt's convention).
+ *   overlap: the output must not overlap the input; undefined.
+ *   scratch: the forward call works in its output and takes none; the inverse call of more than
+ *     one pass (extended_size > 2^8) works in extended_size * batch elements of the leased scratch
+ *     context, which also stages host operands (no allocation per call once it is large enough).
+ *   errors, before any device work and before the first HIP call: INVALID_POINTER for a null input,
+ *     output or config; INVALID_ARGUMENT for the size rules, the config rules, a zero generator, and
+ *     a period that is not a power of two in 1..extended_size with a non-null vanishing_inv.
+ *     extended_size past the domain's order gives INVALID_ARGUMENT once the domain is consulted.
+ *   timing: no branch and no address depends on a field value.                                   */
+/* ------------------------------------------------------------------------------------ */
+/* out[k*extended_size + j] = sum_{i < size} coeffs[k*size + i] * (g * W^j)^i,  j < extended_size,
+ * W = the NTT's root of extended_size */
+eIcicleError mbls_fr_coeff_to_extended(const mbls_fr_t* coeffs, int size, int extended_size,
+                                       const mbls_fr_t* coset_gen, const NTTConfig* config, mbls_fr_t* output);
+/* e[j] = evals[k*extended_size + j] * vanishing_inv[j mod period]   (vanishing_inv == NULL: e = evals)
+ * c[i] = g^-i * N^-1 * sum_j e[j] * W^(-ij);   output[k*out_size + i] = c[i] for i < out_size */
+eIcicleError mbls_fr_extended_to_coeff(const mbls_fr_t* evals, int extended_size, int out_size,
+                                       const mbls_fr_t* coset_gen, const mbls_fr_t* vanishing_inv, int period,
+                                       const NTTConfig* config, mbls_fr_t* output);
+/* host only, no device work: what the calls do for (size, extended_size).  `out` holds 18 words:
+ * out[0] = passes (0 for extended_size 1), out[1] = E, out[2] = DIT stages the forward call skips as
+ * replication = min(E, L of the first pass) (for E beyond it the pruning stops at the first pass: the
+ * second runs in full), out[3] = input rows the first pass reads per tile = 2^(L - out[2]) of 2^L,
+ * out[4] = scratch elements (32 bytes each) of the forward call per member (0), out[5] = scratch
+ * elements of the inverse call per member (staging of host operands not counted; elements, not
+ * bytes: 2^30 of them would not fit the word as bytes), out[6 + 3p ..] = (s0, L, logC) of pass p:
+ * stages s0+1 .. s0+L on tiles of 2^L rows by 2^logC columns, the NTT's own plan.  Words past the
+ * last pass are left alone. */
+eIcicleError mbls_fr_domain_plan(int size, int extended_size, int32_t* out);
+
+/* ------------------------------------------------------------------------------------ */
 /* Fr column sort, and the lookup argument's permuted pair on top of it (step 2 of a halo2-style
  * lookup_prover: permute_expression_pair, between the theta-compression -- mbls_fr_eval_program --
  * and the commitments and grand product -- the MSM and mbls_fr_prefix_product).  (No reference

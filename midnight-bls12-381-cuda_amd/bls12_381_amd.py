@@ -85,6 +85,7 @@ EXPORTED = [
     "mbls_fr_prefix_product", "mbls_fr_poly_divide_linear", "mbls_fr_scan_geometry",
     "mbls_fr_eval_program", "mbls_fr_expr_check",
     "mbls_fr_sort", "mbls_fr_lookup_permute", "mbls_fr_sort_plan",
+    "mbls_fr_coeff_to_extended", "mbls_fr_extended_to_coeff", "mbls_fr_domain_plan",
 ]
 
 _LIB = None
@@ -144,6 +145,8 @@ def lib():
         "mbls_fr_expr_check": [P, i32, i32, i32, i32, P],
         "mbls_fr_sort": [P, sz, b, P, P, P], "mbls_fr_lookup_permute": [P, P, sz, b, P, P, P, P],
         "mbls_fr_sort_plan": [sz, i32, P],
+        "mbls_fr_coeff_to_extended": [P, i32, i32, P, P, P],
+        "mbls_fr_extended_to_coeff": [P, i32, i32, P, P, i32, P, P], "mbls_fr_domain_plan": [i32, i32, P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -688,6 +691,66 @@ def ntt(x, inverse=False, out=None, batch=1, stream=None, is_async=False, coset_
         fn = {"ntt": lib().bls12_381_ntt_cuda, "field": lib().bls12_381_field_ntt_cuda}[entry]
         check(fn(_p(x), n, d, ctypes.byref(cfg), _p(out)), entry)
     return out
+
+
+def _coset_arg(coset_gen):
+    """a host FrC holding the generator's four limbs, or None"""
+    if coset_gen is None:
+        return None
+    g = FrC()
+    for i in range(4):
+        g.limbs[i] = int(coset_gen[i])
+    return ctypes.byref(g)
+
+
+def coeff_to_extended(coeffs, extended_size, coset_gen=None, out=None, stream=None, batch=1, is_async=False):
+    """halo2's coeff_to_extended (mbls_fr_coeff_to_extended): coeffs (batch*size, 4) uint64 Montgomery,
+    size any value in 1..extended_size, numpy (host) or torch (device) -> the polynomial's values on
+    g * H_extended_size, (batch*extended_size, 4).  coset_gen: four Montgomery limbs (host), None for
+    no coset.  Returns `out` when given (it may not overlap coeffs), else storage placed as coeffs is."""
+    size = coeffs.shape[0] // batch
+    if out is None:
+        out = _like(coeffs, batch * extended_size)
+    cfg = ntt_config(batch_size=batch, are_inputs_on_device=_is_dev(coeffs), are_outputs_on_device=_is_dev(out),
+                     is_async=is_async, stream=stream)
+    check(lib().mbls_fr_coeff_to_extended(_p(coeffs), size, extended_size, _coset_arg(coset_gen), ctypes.byref(cfg),
+                                          _p(out)), "mbls_fr_coeff_to_extended")
+    return out
+
+
+def extended_to_coeff(evals, out_size, coset_gen=None, vanishing_inv=None, out=None, stream=None, batch=1,
+                      is_async=False):
+    """halo2's divide_by_vanishing_poly + extended_to_coeff + truncation (mbls_fr_extended_to_coeff):
+    evals (batch*extended_size, 4) uint64 Montgomery values on g * H_extended_size, numpy (host) or
+    torch (device); vanishing_inv (period, 4), placed as evals is, multiplies evals[j] by entry
+    j mod period first (None: no division).  Returns the first out_size coefficients of each member,
+    (batch*out_size, 4): `out` when given (it may not overlap evals), else placed as evals is.  The same
+    coset_gen as in coeff_to_extended undoes its coset."""
+    n = evals.shape[0] // batch
+    assert vanishing_inv is None or _is_dev(vanishing_inv) == _is_dev(evals), "evals and vanishing_inv share one placement"
+    if out is None:
+        out = _like(evals, batch * out_size)
+    cfg = ntt_config(batch_size=batch, are_inputs_on_device=_is_dev(evals), are_outputs_on_device=_is_dev(out),
+                     is_async=is_async, stream=stream)
+    period = 0 if vanishing_inv is None else vanishing_inv.shape[0]
+    check(lib().mbls_fr_extended_to_coeff(_p(evals), n, out_size, _coset_arg(coset_gen), _p(vanishing_inv), period,
+                                          ctypes.byref(cfg), _p(out)), "mbls_fr_extended_to_coeff")
+    return out
+
+
+DOMAIN_PLAN_FIELDS = ("passes", "E", "skipped", "rows", "fwd_scratch", "inv_scratch")
+
+
+def domain_plan(size, extended_size):
+    """what coeff_to_extended / extended_to_coeff do for (size, extended_size) (mbls_fr_domain_plan;
+    host only): dict of DOMAIN_PLAN_FIELDS -- passes, extension bits E, DIT stages skipped as
+    replication, input rows the first pass reads per tile, scratch elements per member of the forward
+    and of the inverse call -- plus plan = [(s0, L, logC)] per pass, the NTT's own"""
+    out = (ctypes.c_int32 * 18)()
+    check(lib().mbls_fr_domain_plan(size, extended_size, out), "mbls_fr_domain_plan")
+    d = dict(zip(DOMAIN_PLAN_FIELDS, list(out)))
+    d["plan"] = [tuple(out[6 + 3 * p:9 + 3 * p]) for p in range(out[0])]
+    return d
 
 
 def ecntt(points, inverse=False, out=None, stream=None, is_async=False):

@@ -27,11 +27,16 @@
 // Algorithmic traffic: 64 B per element per transform (one read + one write of 32 B);
 // actual traffic = passes * 64 B + twiddle reads.  Arithmetic: (n/2) log n Montgomery
 // products -- the kernel is VALU-bound on gfx950.
+//
+// The extended-coset transforms of a halo2-style EvaluationDomain (mbls_fr_coeff_to_extended,
+// mbls_fr_extended_to_coeff) live at the end of the file: first and last passes of their own
+// (k_dom_pass) around the passes above.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include <memory>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "mbls_common.hpp"
@@ -82,9 +87,32 @@ struct DomainTables {
     }
 };
 
+// Coset power tables of the extended-coset transforms (see the domain section below): built once
+// per (generator, size, direction) and cached in the device's domain, with the same lifetime rule
+// as DomainTables -- a caller enqueues with a shared_ptr snapshot, and the memory is freed after a
+// device synchronisation when the last snapshot is dropped.
+struct CosetTables {
+    int device = 0;
+    uint64_t g[4] = {0, 0, 0, 0};  // the caller's generator (Montgomery), the cache key with:
+    int log_n = 0, sh = 0;         // transform size and index split i = ((i >> sh) << sh) + (i & (2^sh - 1))
+    bool inverse = false;
+    uint8_t* mem = nullptr;        // A (2^(log_n - sh) entries) then B (2^sh entries), 32 B each
+    const uint4* A = nullptr;      // forward g^(t << sh); inverse N^-1 g^-(t << sh)
+    const uint4* B = nullptr;      // forward g^c; inverse g^-c
+    ~CosetTables() {
+        int cur = 0;
+        (void)hipGetDevice(&cur);
+        if (cur != device) (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();  // every transform that read the tables has finished
+        if (mem) (void)hipFree(mem);
+        if (cur != device) (void)hipSetDevice(cur);
+    }
+};
+
 struct Domain {
     int order_log = 32;  // 2^order_log: order of the initialised root (size bound)
     std::shared_ptr<DomainTables> tables;
+    std::vector<std::shared_ptr<CosetTables>> cosets;  // most recently used first, <= MAX_COSETS
 };
 
 static constexpr int MAX_DOMAIN_DEVICES = 64;
@@ -572,10 +600,12 @@ eIcicleError ntt_init_domain(const mbls_fr_t* root, const NTTInitDomainConfig* c
 
 eIcicleError ntt_release_domain() {
     std::shared_ptr<DomainTables> old;
+    std::vector<std::shared_ptr<CosetTables>> old_cosets;
     {
         std::lock_guard<std::mutex> lk(g_domain_mu);
         Domain* dom = current_domain();
         if (!dom) return MBLS_INVALID_DEVICE;
+        old_cosets.swap(dom->cosets);
         old = std::move(dom->tables);
         dom->tables.reset();
         dom->order_log = 32;
@@ -742,6 +772,425 @@ eIcicleError ntt_domain_roots(int log_n, bool inverse, uint64_t* w, uint64_t* n_
 }
 bool fr_is_montgomery_one(const uint64_t* a) { return hfr_eq(a, HFR_ONE); }
 
+// ---------------------------------------------------------------------------------------------
+// Extended-coset transforms: halo2's EvaluationDomain::coeff_to_extended and extended_to_coeff
+// (DESIGN.md 5.12).  Same pass plan, tiles, twiddles and butterflies as ntt_device; the first and
+// last passes are k_dom_pass, the passes between them are k_ntt_pass<false, ...> as they stand.
+//
+// Forward (size coefficients -> N = 2^K values on g H_N), E = K - log2(next_pow2(size)):
+//   the first pass's tile rows are the indices (t << colbits) + col, so only rows t < 2^(L - Ee),
+//   Ee = min(E, L), can hold a coefficient.  They are loaded (an index >= size reads as zero),
+//   multiplied by g^i, and written to their bit-reversed row p << Ee and to the 2^Ee - 1 rows below
+//   it: DIT stages 1..Ee of a group whose other inputs are zero only copy ((a, 0) -> (a, a)).  The
+//   butterflies start at stage Ee + 1.  For E > L the pruning is capped at the first pass: the
+//   second pass runs in full.  The output buffer is the working buffer: no scratch.
+// Inverse (N values -> out_size coefficients): the first pass multiplies by vanishing_inv[j mod
+//   period] on load, the last pass multiplies every output by N^-1 g^-i and stores i < out_size.
+//   A transform of more than one pass works in an N-element scratch array per member.
+// Coset powers: the index splits as the tile does, i = (t << sh) + c (forward sh = colbits of the
+//   first pass, inverse sh = s0 of the last), so g^(+-i) = A[t] B[c] with two small tables
+//   (2^(K - sh) and 2^sh entries; 2^8 + 2^14 forward and 2^7 + 2^15 inverse at 2^22) and two
+//   products per element.  The tables are cached in the device's domain, keyed by (generator, K,
+//   sh, direction): a prover uses one generator for the whole proof, and a cached table lets the
+//   forward call run without a scratch lease (whose event would hold the next dispatch ~5 us).
+// Lazy range: a loaded value is canonical (the input contract) and the table entries are canonical,
+//   so each reducing Montgomery product (Fr operator*, a < 2r, b < r -> canonical) enters the tile
+//   below r, inside the butterflies' [0, 2r).  The last pass's values are < 2r and its first product
+//   is by a canonical A[t]: canonical, as the SCALE product of k_ntt_pass.
+struct DomArgs {
+    uint32_t in_stride, out_stride;  // elements between batch members
+    uint32_t in_size;                // forward FIRST: coefficients per member
+    uint32_t out_size;               // inverse LAST: coefficients kept per member
+    int E;                           // forward FIRST: replication stages skipped (<= L)
+    int sh;                          // coset index split
+    const uint4* tabA;               // CosetTables::A, or null: no coset
+    const uint4* tabB;               // CosetTables::B
+    const uint4* vinv;               // inverse FIRST: vanishing_inv, or null
+    uint32_t vmask;                  // period - 1
+    Fr scale;                        // inverse LAST without a coset: N^-1
+};
+
+template <bool FIRST, bool LAST, bool INV>
+__global__ __launch_bounds__(NTT_THREADS, 5) void k_dom_pass(uint8_t* __restrict__ out_,
+                                                                         const uint8_t* __restrict__ in_,
+                                                                         const uint8_t* __restrict__ tw_,
+                                                                         uint32_t tw_count, int log_n, int s0, int L,
+                                                                         int logC, uint32_t ntiles, DomArgs A) {
+    __shared__ uint4 lds[NTT_TILE * 2];
+    const uint32_t C = 1u << logC;
+    const uint32_t rows = 1u << L;
+    const uint32_t T = rows * C;
+    const uint32_t tiles_per_poly = (uint32_t)(((size_t)1 << log_n) >> (L + logC));
+    const uint4* twa = reinterpret_cast<const uint4*>(tw_);
+    const uint4* twb = twa + tw_count;
+    const uint32_t* twc = reinterpret_cast<const uint32_t*>(twa + 2 * (size_t)tw_count);
+    const uint32_t colbits = (uint32_t)(log_n - L);
+    const uint32_t lo_tiles = FIRST ? 1u : (1u << s0) >> logC;
+    const uint32_t id = blockIdx.x;  // one tile per workgroup
+    if (id >= ntiles) return;
+    const uint32_t poly = id / tiles_per_poly, tile = id % tiles_per_poly;
+    const uint32_t lo0 = FIRST ? tile * C : (tile % lo_tiles) * C;
+    const uint32_t hi_base = FIRST ? 0u : (tile / lo_tiles) << (s0 + L);
+    const uint4* in = reinterpret_cast<const uint4*>(in_) + 2 * (size_t)poly * A.in_stride;
+    uint4* o = reinterpret_cast<uint4*>(out_) + 2 * (size_t)poly * A.out_stride;
+    const uint32_t smask = (1u << A.sh) - 1;
+    const int Ee = (FIRST && !INV) ? A.E : 0;
+
+    if (FIRST) {
+        // rows t < 2^(L - Ee) only; each lands on its bit-reversed DIT row and its replicas
+        const uint32_t Tl = T >> Ee;
+#pragma clang loop vectorize(disable) interleave(disable)
+        for (uint32_t e = threadIdx.x; e < Tl; e += NTT_THREADS) {
+            const uint32_t c = e & (C - 1), t = e >> logC;
+            const uint32_t idx = (t << colbits) + lo0 + c;
+            Fr v;
+            if (INV) {
+                v = ld2(in, idx);
+                if (A.vinv) v = v * ld2(A.vinv, idx & A.vmask);  // canonical * canonical
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v.v[k] = 0;
+                if (idx < A.in_size) v = ld2(in, idx);
+                // canonical v times canonical g^(t << sh), then times canonical g^c: canonical
+                if (A.tabA) v = (v * ld2(A.tabA, idx >> A.sh)) * ld2(A.tabB, idx & smask);
+            }
+            const uint32_t p = bitrev(t, L - Ee) << Ee;
+            for (uint32_t r = 0; r < (1u << Ee); ++r) st2(lds, (p + r) * C + c, v);
+        }
+    } else {
+#pragma clang loop vectorize(disable) interleave(disable)
+        for (uint32_t e = threadIdx.x; e < T; e += NTT_THREADS)
+            st2(lds, e, ld2(in, hi_base + ((e >> logC) << s0) + lo0 + (e & (C - 1))));
+    }
+    __syncthreads();
+    const uint32_t lo_base = FIRST ? 0u : lo0;
+    // the last store of a value at position dst of its member
+    auto fin_store = [&](uint32_t dst, Fr v) {
+        if (INV && LAST) {
+            // v < 2r: the first product is by a canonical factor and reduces
+            if (A.tabA) v = (v * ld2(A.tabA, dst >> A.sh)) * ld2(A.tabB, dst & smask);
+            else v = v * A.scale;
+            if (dst < A.out_size) st2(o, dst, v);
+        } else {
+            if (LAST) reduce_once(v);
+            st2(o, dst, v);
+        }
+    };
+    auto put = [&](uint32_t row, uint32_t c, const Fr& v) {
+        fin_store(FIRST ? (bitrev(lo0 + c, colbits) << L) + row : hi_base + (row << s0) + lo0 + c, v);
+    };
+    // one stage pair; TRIV: the first pair of an unpruned first pass (j = 0, twiddles 1)
+    auto pair = [&](int l, auto triv_c) {
+        constexpr bool triv = decltype(triv_c)::value;
+        const bool fin = l + 2 > L;
+        const uint32_t h = 1u << (l - 1);
+        const int s = s0 + l;
+        const uint32_t t1 = (1u << (s - 1)) - 1, t2 = (1u << s) - 1;
+        const uint32_t stride = h * C;
+        for (uint32_t u = threadIdx.x; u < T / 4; u += NTT_THREADS) {
+            const uint32_t c = u & (C - 1);
+            const uint32_t r = u >> logC;
+            const uint32_t j = r & (h - 1);
+            const uint32_t q = ((r >> (l - 1)) << (l + 1)) + j;
+            const uint32_t e0 = q * C + c;
+            const uint32_t lo = FIRST ? 0u : lo_base + c;
+            r29::F29 w1, w2, w3;
+            const uint32_t jl = (j << s0) + lo;
+            if (!triv) {
+                w1 = ldtw(twa, twb, twc, t1 + jl);
+                w2 = ldtw(twa, twb, twc, t2 + jl);
+            }
+            w3 = ldtw(twa, twb, twc, t2 + jl + (h << s0));
+            Fr x0 = ld2(lds, e0), x1 = ld2(lds, e0 + stride), x2 = ld2(lds, e0 + 2 * stride),
+               x3 = ld2(lds, e0 + 3 * stride);
+            if (!triv) {
+                x1 = r29::mul_words(x1, w1);
+                x3 = r29::mul_words(x3, w1);
+            }
+            Fr y0 = add_2r(x0, x1), y1 = sub_2r(x0, x1), y2 = add_2r(x2, x3), y3 = sub_2r(x2, x3);
+            if (!triv) y2 = r29::mul_words(y2, w2);
+            y3 = r29::mul_words(y3, w3);
+            if (fin) {
+                put(q, c, add_2r(y0, y2));
+                put(q + 2 * h, c, sub_2r(y0, y2));
+                put(q + h, c, add_2r(y1, y3));
+                put(q + 3 * h, c, sub_2r(y1, y3));
+            } else {
+                st2(lds, e0, add_2r(y0, y2));
+                st2(lds, e0 + 2 * stride, sub_2r(y0, y2));
+                st2(lds, e0 + stride, add_2r(y1, y3));
+                st2(lds, e0 + 3 * stride, sub_2r(y1, y3));
+            }
+        }
+    };
+    int l = Ee + 1;
+    for (; l + 1 <= L; l += 2) {
+        if (FIRST && l == 1) pair(l, std::true_type{});
+        else pair(l, std::false_type{});
+        if (l + 2 > L) return;
+        __syncthreads();
+    }
+    if (l == L) {  // one radix-2 stage left
+        const uint32_t half = 1u << (l - 1);
+        const int s = s0 + l;
+        const uint32_t ts = (1u << (s - 1)) - 1;
+        for (uint32_t u = threadIdx.x; u < T / 2; u += NTT_THREADS) {
+            const uint32_t c = u & (C - 1);
+            const uint32_t r = u >> logC;
+            const uint32_t gg = r >> (l - 1);
+            const uint32_t j = r & (half - 1);
+            const uint32_t t0 = (gg << l) + j, t1 = t0 + half;
+            r29::F29 w;
+            if (l > 1 || !FIRST) w = ldtw(twa, twb, twc, ts + (j << s0) + (FIRST ? 0u : lo_base + c));
+            const Fr a = ld2(lds, t0 * C + c);
+            Fr b = ld2(lds, t1 * C + c);
+            if (l > 1 || !FIRST) b = r29::mul_words(b, w);
+            put(t0, c, add_2r(a, b));
+            put(t1, c, sub_2r(a, b));
+        }
+        return;
+    }
+    // ---- no stage left (L == 0, or every stage of the pass was replication): store the tile
+    for (uint32_t e = threadIdx.x; e < T; e += NTT_THREADS) {
+        if (FIRST) {
+            const uint32_t p = e & (rows - 1), c = e >> L;
+            put(p, c, ld2(lds, p * C + c));
+        } else {
+            put(e >> logC, e & (C - 1), ld2(lds, e));
+        }
+    }
+}
+
+// size-1 transforms: out = in (* vanishing_inv[0]); g^0 = N^-1 = 1
+__global__ void k_dom_point(uint8_t* out, const uint8_t* in, const uint8_t* vinv, size_t count) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    Fr v = load<FrCfg>(in + 32 * i);
+    if (vinv) v = v * load<FrCfg>(vinv);
+    store<FrCfg>(out + 32 * i, v);
+}
+
+// A[t] = scale * g^(t << sh), t < nA;  B[c] = g^c, c < nB (one ladder per table entry, build only)
+__global__ void k_dom_tables(uint8_t* A, uint32_t nA, uint8_t* B, uint32_t nB, Fr g, int sh, Fr scale) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nA + nB) return;
+    uint64_t e = i < nA ? (uint64_t)i << sh : (uint64_t)(i - nA);
+    Fr acc = Fr::one(), b = g;
+    while (e) {
+        if (e & 1) acc = acc * b;
+        b = sqr(b);
+        e >>= 1;
+    }
+    if (i < nA) store<FrCfg>(A + 32 * (size_t)i, acc * scale);
+    else store<FrCfg>(B + 32 * (size_t)(i - nA), acc);
+}
+
+static constexpr size_t MAX_COSETS = 8;
+static constexpr int DOM_MAX_LOG = 30;   // as ntt_call: sizes are ints, indices 32-bit
+static constexpr int DOM_MAX_PASSES = 4; // ceil(30 / 8)
+
+// ntt_device's pass plan: (s0, L, logC) per pass; returns the pass count (0 for log_n == 0)
+static int dom_passes(int log_n, int (*pl)[3]) {
+    const int npass = (log_n + NTT_PASS_STAGES - 1) / NTT_PASS_STAGES;
+    int s0 = 0;
+    for (int p = 0; p < npass; ++p) {
+        const int remaining = log_n - s0;
+        const int L = (remaining + (npass - p) - 1) / (npass - p);
+        const int colspace = p == 0 ? (log_n - L) : s0;
+        int logC = NTT_TILE_LOG - L;
+        if (logC > colspace) logC = colspace;
+        pl[p][0] = s0, pl[p][1] = L, pl[p][2] = logC;
+        s0 += L;
+    }
+    return npass;
+}
+
+static int ceil_log2(long long n) {
+    int k = 0;
+    while ((1LL << k) < n) ++k;
+    return k;
+}
+
+static eIcicleError domain_plan(int size, int extended_size, int32_t* out) {
+    if (!out) return MBLS_INVALID_POINTER;
+    const int K = log2_exact(extended_size);
+    if (K < 0 || K > DOM_MAX_LOG || size < 1 || size > extended_size) return MBLS_INVALID_ARGUMENT;
+    int pl[DOM_MAX_PASSES][3];
+    const int np = dom_passes(K, pl);
+    const int E = K - ceil_log2(size);
+    const int L0 = np ? pl[0][1] : 0;
+    const int Ee = E < L0 ? E : L0;
+    out[0] = np;
+    out[1] = E;
+    out[2] = Ee;
+    out[3] = 1 << (L0 - Ee);
+    out[4] = 0;                      // the forward call works in its output
+    out[5] = np > 1 ? 1 << K : 0;    // elements of 32 bytes (2^30 of them would not fit as bytes)
+    for (int p = 0; p < np; ++p)
+        for (int k = 0; k < 3; ++k) out[6 + 3 * p + k] = pl[p][k];
+    return MBLS_SUCCESS;
+}
+
+// the coset tables of (g, log_n, sh, inverse) on the current device, built on `st` (and waited
+// for, once) when the cache lacks them; caller holds g_domain_mu.  `evicted` takes a table pushed
+// out of the cache: the caller drops it after releasing the lock (its destructor synchronises).
+static eIcicleError coset_tables(Domain& dom, const uint64_t* g, int log_n, int sh, bool inverse, hipStream_t st,
+                                 std::shared_ptr<CosetTables>& got, std::shared_ptr<CosetTables>& evicted) {
+    for (size_t k = 0; k < dom.cosets.size(); ++k) {
+        const CosetTables& c = *dom.cosets[k];
+        if (c.log_n == log_n && c.sh == sh && c.inverse == inverse && hfr_eq(c.g, g)) {
+            got = dom.cosets[k];
+            dom.cosets.erase(dom.cosets.begin() + k);
+            dom.cosets.insert(dom.cosets.begin(), got);
+            return MBLS_SUCCESS;
+        }
+    }
+    auto t = std::make_shared<CosetTables>();
+    MBLS_TRY(hipGetDevice(&t->device));
+    const uint32_t nA = 1u << (log_n - sh), nB = 1u << sh;
+    MBLS_TRY(hipMalloc(&t->mem, 32 * ((size_t)nA + nB)));
+    memcpy(t->g, g, 32);
+    t->log_n = log_n, t->sh = sh, t->inverse = inverse;
+    t->A = reinterpret_cast<const uint4*>(t->mem);
+    t->B = t->A + 2 * (size_t)nA;
+    uint64_t base[4], scale[4];
+    memcpy(base, g, 32);
+    memcpy(scale, HFR_ONE, 32);
+    if (inverse) {
+        hfr_inv(base, g);
+        uint64_t nm[4] = {(uint64_t)1 << log_n, 0, 0, 0};
+        hfr_mul(nm, nm, HFR_R2);
+        hfr_inv(scale, nm);
+    }
+    hipLaunchKernelGGL(k_dom_tables, dim3((nA + nB + 255) / 256), dim3(256), 0, st, t->mem, nA, t->mem + 32 * (size_t)nA,
+                       nB, to_dev(base), sh, to_dev(scale));
+    MBLS_TRY(hipGetLastError());
+    MBLS_TRY(hipStreamSynchronize(st));  // another stream may use the cached tables next
+    dom.cosets.insert(dom.cosets.begin(), t);
+    if (dom.cosets.size() > MAX_COSETS) {
+        evicted = std::move(dom.cosets.back());
+        dom.cosets.pop_back();
+    }
+    got = std::move(t);
+    return MBLS_SUCCESS;
+}
+
+// Both directions: validation (before any HIP call), the domain's tables, staging, the passes.
+//   forward: input = coeffs (in_count = size), output = N values; vinv unused
+//   inverse: input = N evaluations, output = out_count coefficients
+static eIcicleError domain_call(bool inverse, const mbls_fr_t* input, int in_count, int extended_size, int out_count,
+                                const mbls_fr_t* coset_gen, const mbls_fr_t* vanishing_inv, int period,
+                                const NTTConfig* cfg, mbls_fr_t* output) {
+    if (!input || !output || !cfg) return MBLS_INVALID_POINTER;
+    const int K = log2_exact(extended_size);
+    if (K < 0 || K > DOM_MAX_LOG) return MBLS_INVALID_ARGUMENT;
+    const int part = inverse ? out_count : in_count;  // size or out_size
+    if (part < 1 || part > extended_size) return MBLS_INVALID_ARGUMENT;
+    if (cfg->columns_batch || (int)cfg->ordering != MBLS_ORDERING_NN) return MBLS_INVALID_ARGUMENT;
+    if (inverse && vanishing_inv && (log2_exact(period) < 0 || period > extended_size)) return MBLS_INVALID_ARGUMENT;
+    bool coset = false;
+    uint64_t g[4];
+    if (coset_gen) {
+        memcpy(g, coset_gen->limbs, 32);
+        uint64_t gr[4];
+        hfr_mul(gr, g, HFR_R2);  // g R mod r, canonical for any 256-bit g
+        const uint64_t zero[4] = {0, 0, 0, 0};
+        if (hfr_eq(gr, zero)) return MBLS_INVALID_ARGUMENT;
+        coset = !hfr_eq(g, HFR_ONE);
+    }
+    const int batch = cfg->batch_size > 0 ? cfg->batch_size : 1;
+    const size_t N = (size_t)1 << K;
+    int pl[DOM_MAX_PASSES][3];
+    const int np = dom_passes(K, pl);
+    for (int p = 0; p < np; ++p)
+        if ((N >> (pl[p][1] + pl[p][2])) * (size_t)batch > 0x7fffffff) return MBLS_INVALID_ARGUMENT;
+    hipStream_t st = static_cast<hipStream_t>(cfg->stream);
+    // forward: i = (t << colbits) + c of the first pass; inverse: i = (row << s0) + lo of the last
+    const int sh = np ? (inverse ? pl[np - 1][0] : K - pl[0][1]) : 0;
+
+    std::shared_ptr<DomainTables> tables, superseded;
+    std::shared_ptr<CosetTables> ctab, evicted;
+    {
+        std::lock_guard<std::mutex> lk(g_domain_mu);
+        Domain* dom = current_domain();
+        if (!dom) return MBLS_INVALID_DEVICE;
+        if (K > dom->order_log) return MBLS_INVALID_ARGUMENT;  // beyond the initialised root
+        if (!dom->tables || dom->tables->max_log < K) {
+            int want = K < 20 ? 20 : K;
+            if (want > dom->order_log) want = dom->order_log;
+            eIcicleError er = build_domain(*dom, want, st, superseded);
+            if (er != MBLS_SUCCESS) return er;
+        }
+        tables = dom->tables;
+        if (coset && np) {
+            eIcicleError er = coset_tables(*dom, g, K, sh, inverse, st, ctab, evicted);
+            if (er != MBLS_SUCCESS) return er;
+        }
+    }
+    const bool in_dev = cfg->are_inputs_on_device, out_dev = cfg->are_outputs_on_device;
+    const size_t in_stride = inverse ? N : (size_t)in_count, out_stride = inverse ? (size_t)out_count : N;
+    Staging S(st, Staging::LEASE_IF_STAGED);
+    const uint8_t *src, *vdev = nullptr;
+    uint8_t *dst, *work = nullptr;
+    S.in(&src, input, in_stride * 32 * batch, in_dev);
+    if (inverse && vanishing_inv) S.in(&vdev, vanishing_inv, (size_t)period * 32, in_dev);
+    S.out(&dst, output, out_stride * 32 * batch, out_dev);
+    if (inverse && np > 1) S.scratch(&work, N * 32 * batch);  // the input is const, the output too short
+    eIcicleError er = S.open();
+    if (er != MBLS_SUCCESS) return er;
+
+    if (np == 0) {
+        hipLaunchKernelGGL(k_dom_point, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, dst, src, vdev,
+                           (size_t)batch);
+        MBLS_TRY(hipGetLastError());
+        return S.close(cfg->is_async);
+    }
+    DomArgs A;
+    A.in_stride = (uint32_t)in_stride, A.out_stride = (uint32_t)out_stride;
+    A.in_size = (uint32_t)in_count, A.out_size = (uint32_t)out_count;
+    const int E = inverse ? 0 : K - ceil_log2(in_count);
+    A.E = E < pl[0][1] ? E : pl[0][1];
+    A.sh = sh;
+    A.tabA = ctab ? ctab->A : nullptr, A.tabB = ctab ? ctab->B : nullptr;
+    A.vinv = reinterpret_cast<const uint4*>(vdev), A.vmask = vdev ? (uint32_t)period - 1 : 0;
+    uint64_t ninv_h[4];
+    memcpy(ninv_h, HFR_ONE, 32);
+    if (inverse) {
+        uint64_t nm[4] = {N, 0, 0, 0};
+        hfr_mul(nm, nm, HFR_R2);
+        hfr_inv(ninv_h, nm);
+    }
+    A.scale = to_dev(ninv_h);
+    const uint8_t* tw = inverse ? tables->tw_inv : tables->tw;
+    const uint32_t twn = tables->count;
+    uint8_t* wbuf = inverse ? work : dst;  // where the passes between the first and the last work
+    ProfScope prof_t(inverse ? "domain.extended_to_coeff" : "domain.coeff_to_extended", st);
+    for (int p = 0; p < np; ++p) {
+        const int s0 = pl[p][0], L = pl[p][1], logC = pl[p][2];
+        const bool first = p == 0, last = p == np - 1;
+        const uint32_t nt = (uint32_t)((N >> (L + logC)) * (size_t)batch);
+        dim3 grid(nt), blk(NTT_THREADS);
+        DomArgs a = A;
+        if (first && last) {
+            if (inverse) hipLaunchKernelGGL((k_dom_pass<true, true, true>), grid, blk, 0, st, dst, src, tw, twn, K, s0, L, logC, nt, a);
+            else hipLaunchKernelGGL((k_dom_pass<true, true, false>), grid, blk, 0, st, dst, src, tw, twn, K, s0, L, logC, nt, a);
+        } else if (first) {
+            a.out_stride = (uint32_t)N;
+            if (inverse) hipLaunchKernelGGL((k_dom_pass<true, false, true>), grid, blk, 0, st, wbuf, src, tw, twn, K, s0, L, logC, nt, a);
+            else hipLaunchKernelGGL((k_dom_pass<true, false, false>), grid, blk, 0, st, wbuf, src, tw, twn, K, s0, L, logC, nt, a);
+        } else if (last && inverse) {
+            a.in_stride = (uint32_t)N;
+            hipLaunchKernelGGL((k_dom_pass<false, true, true>), grid, blk, 0, st, dst, wbuf, tw, twn, K, s0, L, logC, nt, a);
+        } else if (last) {
+            hipLaunchKernelGGL((k_ntt_pass<false, true, false>), grid, blk, 0, st, wbuf, wbuf, tw, twn, K, s0, L, logC, A.scale, nt);
+        } else {
+            hipLaunchKernelGGL((k_ntt_pass<false, false, false>), grid, blk, 0, st, wbuf, wbuf, tw, twn, K, s0, L, logC, A.scale, nt);
+        }
+        MBLS_TRY(hipGetLastError());
+    }
+    return S.close(cfg->is_async);
+}
+
 }  // namespace mbls
 
 using namespace mbls;
@@ -768,6 +1217,20 @@ eIcicleError bls12_381_field_ntt_init_domain_cuda(const mbls_fr_t* root_of_unity
     return ntt_init_domain(root_of_unity, config);
 }
 eIcicleError bls12_381_field_ntt_release_domain_cuda(void) { return ntt_release_domain(); }
+
+eIcicleError mbls_fr_coeff_to_extended(const mbls_fr_t* coeffs, int size, int extended_size, const mbls_fr_t* coset_gen,
+                                       const NTTConfig* config, mbls_fr_t* output) {
+    return domain_call(false, coeffs, size, extended_size, extended_size, coset_gen, nullptr, 0, config, output);
+}
+eIcicleError mbls_fr_extended_to_coeff(const mbls_fr_t* evals, int extended_size, int out_size,
+                                       const mbls_fr_t* coset_gen, const mbls_fr_t* vanishing_inv, int period,
+                                       const NTTConfig* config, mbls_fr_t* output) {
+    return domain_call(true, evals, extended_size, extended_size, out_size, coset_gen, vanishing_inv, period, config,
+                       output);
+}
+eIcicleError mbls_fr_domain_plan(int size, int extended_size, int32_t* out) {
+    return domain_plan(size, extended_size, out);
+}
 
 // ICICLE get_root_of_unity_from_domain (registered as NttGetRouFromDomainImpl,
 // icicle_backend_api.cuh:135-138): w_(2^logn) of the initialised domain, Montgomery form
