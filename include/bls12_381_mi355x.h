@@ -369,6 +369,70 @@ eIcicleError mbls_fr_lookup_permute(const mbls_fr_t* input, const mbls_fr_t* tab
 eIcicleError mbls_fr_sort_plan(size_t size, int batch, int64_t* out);
 
 /* ------------------------------------------------------------------------------------ */
+/* Log-derivative lookup ("mv-lookup", LogUp) of halo2 forks: the multiplicity column m, an Fr running
+ * sum, and the running sum phi of the lookup's terms.  After the theta-compression
+ * (mbls_fr_eval_program) a lookup is mbls_fr_lookup_multiplicities then mbls_fr_logup_sum on one
+ * stream; the MSMs for m and phi read device memory.  (No reference counterpart: the reference tree
+ * uses the classic lookup, on the CPU.  The definitions are this library's own.)
+ *   elements: 32 bytes, canonical (< r).  mbls_fr_lookup_multiplicities reads Montgomery elements when
+ *     `montgomery` is set, else standard form, and writes m in the same form; the two sums read and
+ *     write Montgomery elements.  Every output element is canonical.
+ *   equality (the join): of the canonical 32-byte elements.  A non-canonical element gets an
+ *     unspecified count; it never causes an out-of-range access.
+ *   pointer table: `inputs` is HOST memory, always: n_inputs column pointers, as `columns` is for
+ *     mbls_fr_eval_program; n_inputs in 1..64.
+ *   batch: config->batch_size members (0 counts as 1), row-major, each of `size` elements, in the
+ *     table, the multiplicities, the output and every input column alike; a member's cells are
+ *     matched against that member's table only.  beta, init, total and n_missing hold one entry per
+ *     member.  columns_batch gives API_NOT_IMPLEMENTED, as the scans do.
+ *   placement: config->is_a_on_device every input column, table and multiplicities-as-input (all
+ *     alike; mbls_fr_prefix_sum: input), is_b_on_device beta and init, is_result_on_device the vector
+ *     output and total.  Host operands are staged through the leased scratch context, which also
+ *     holds every work array (no allocation per call once it is large enough); a host output makes
+ *     the call synchronous, otherwise it synchronises unless is_async.
+ *   scratch bytes, n = size * batch, staging of host operands not counted (each staged column is
+ *     32 n): mbls_fr_lookup_multiplicities out[4] of mbls_fr_sort_plan(size, batch) + 8 (n + batch),
+ *     about 56 n; mbls_fr_prefix_sum 64 * batch * G for G = out[2] of mbls_fr_scan_geometry(size);
+ *     mbls_fr_logup_sum 64 n + 64 * batch * G.  Every block is rounded up to 256 bytes.
+ *   errors, all before any device work: INVALID_POINTER for a null inputs, table, multiplicities,
+ *     beta, input, output or config, or a null entry of inputs; INVALID_ARGUMENT for size == 0,
+ *     size * batch > 2^26, or n_inputs outside 1..64.
+ *   in place and overlap: mbls_fr_prefix_sum's output may equal its input, mbls_fr_logup_sum's output
+ *     may equal multiplicities (the same pointer); any other overlap is undefined.
+ *   timing: mbls_fr_lookup_multiplicities is NOT constant time: the sort's digit bins and skipped
+ *     key words, the search path and the merging of equal rows depend on the values, as in
+ *     mbls_fr_sort.  mbls_fr_prefix_sum and mbls_fr_logup_sum have no branch and no address that
+ *     depends on a field value; zero denominators go through mask selects and the fixed Fermat chain,
+ *     as in bls12_381_batch_inv_cuda.                                                            */
+/* ------------------------------------------------------------------------------------ */
+/* m[k*size + j] = #{ (c, i) : c < n_inputs, i < size, inputs[c][k*size + i] == table[k*size + j] }
+ *                 if j is the CREDITED row of its value in member k's table, else 0.
+ * The credited row of a value is the lowest row of the member's table that holds it
+ * (credit_last: the highest).  m is written as an Fr element: the count, Montgomery when
+ * `montgomery` is set, else standard form; always canonical.
+ * n_missing: HOST pointer to `batch` counts, n_missing[k] = the cells (c, i) of member k whose
+ * value its table lacks; may be NULL; non-NULL makes the call synchronous.  Missing cells are
+ * data, not an error (SUCCESS), as in mbls_fr_lookup_permute: sum_j m[j] + n_missing[k] =
+ * n_inputs * size for every member. */
+eIcicleError mbls_fr_lookup_multiplicities(const mbls_fr_t* const* inputs, int n_inputs, const mbls_fr_t* table,
+                                           size_t size, bool montgomery, bool credit_last,
+                                           const VecOpsConfig* config, mbls_fr_t* multiplicities,
+                                           uint64_t* n_missing);
+/* out[k*size + i] = init[k] + sum_{j < i} in[k*size + j]   (inclusive: j <= i);
+ * total[k] = init[k] + sum over all j.  init == NULL means zero.  total may be NULL.  The geometry is
+ * mbls_fr_scan_geometry's; a step is one modular addition. */
+eIcicleError mbls_fr_prefix_sum(const mbls_fr_t* input, size_t size, const mbls_fr_t* init, bool inclusive,
+                                const VecOpsConfig* config, mbls_fr_t* output, mbls_fr_t* total);
+/* term[i] = sum_{c < n_inputs} (inputs[c][i] + beta[k])^-1  -  m[i] * (table[i] + beta[k])^-1
+ * output = the EXCLUSIVE prefix sum of term from init[k] (phi[0] = init, phi[i+1] = phi[i] + term[i]);
+ * total[k] = phi[size].  Montgomery elements throughout.  0^-1 = 0, as bls12_381_batch_inv_cuda.
+ * init == NULL means zero, total may be NULL.  With phi[0] = 0 a satisfied lookup has total == 0. */
+eIcicleError mbls_fr_logup_sum(const mbls_fr_t* const* inputs, int n_inputs, const mbls_fr_t* table,
+                               const mbls_fr_t* multiplicities, size_t size, const mbls_fr_t* beta,
+                               const mbls_fr_t* init, const VecOpsConfig* config, mbls_fr_t* output,
+                               mbls_fr_t* total);
+
+/* ------------------------------------------------------------------------------------ */
 /* Fr expression evaluator: one caller-supplied straight-line stack program run once per row over
  * a set of columns read at rotated rows -- the permutation numerators and denominators that feed
  * mbls_fr_prefix_product, the theta-compression of lookup columns, the gate / permutation / lookup

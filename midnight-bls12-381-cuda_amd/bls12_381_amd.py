@@ -86,6 +86,7 @@ EXPORTED = [
     "mbls_fr_eval_program", "mbls_fr_expr_check",
     "mbls_fr_sort", "mbls_fr_lookup_permute", "mbls_fr_sort_plan",
     "mbls_fr_coeff_to_extended", "mbls_fr_extended_to_coeff", "mbls_fr_domain_plan",
+    "mbls_fr_lookup_multiplicities", "mbls_fr_prefix_sum", "mbls_fr_logup_sum",
 ]
 
 _LIB = None
@@ -147,6 +148,8 @@ def lib():
         "mbls_fr_sort_plan": [sz, i32, P],
         "mbls_fr_coeff_to_extended": [P, i32, i32, P, P, P],
         "mbls_fr_extended_to_coeff": [P, i32, i32, P, P, i32, P, P], "mbls_fr_domain_plan": [i32, i32, P],
+        "mbls_fr_lookup_multiplicities": [P, i32, P, sz, b, b, P, P, P],
+        "mbls_fr_prefix_sum": [P, sz, P, b, P, P, P], "mbls_fr_logup_sum": [P, i32, P, P, sz, P, P, P, P, P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -604,6 +607,80 @@ def lookup_permute(input, table, *, mont=True, batch=1, count=True, out=None, st
     check(lib().mbls_fr_lookup_permute(_p(input), _p(table), n, bool(mont), ctypes.byref(cfg), _p(pin), _p(ptab), cnt),
           "mbls_fr_lookup_permute")
     return pin, ptab, ([int(v) for v in cnt] if count else None)
+
+
+# ----------------------------------------------------------------------------- log-derivative lookup
+def _column_table(inputs, like):
+    n, on_dev = like.shape[0], _is_dev(like)
+    assert all(c.shape[0] == n and _is_dev(c) == on_dev for c in inputs), "columns and table share one size and placement"
+    return (ctypes.c_void_p * len(inputs))(*[_p(c) for c in inputs])
+
+
+def lookup_multiplicities(inputs, table, credit="first", montgomery=True, *, batch=1, count=True, out=None, stream=None,
+                          is_async=False):
+    """The log-derivative lookup's multiplicity column (mbls_fr_lookup_multiplicities).  inputs: a
+    list of 1..64 columns, table: (batch*n, 4) uint64, Montgomery unless montgomery is False, all
+    numpy (host) or all torch (device).  Returns (m, n_missing): m[j] = the input cells equal to
+    table[j] as a field element in the inputs' form if j is the credited row of its value -- the
+    lowest row holding it, credit="last": the highest -- else zero; `out` when given, else placed as
+    the table is.  n_missing: a list of `batch` counts of cells whose value the table lacks, or None
+    for count=False (then a device output with is_async does not wait)."""
+    assert credit in ("first", "last")
+    n = table.shape[0] // batch
+    cols = _column_table(inputs, table)
+    if out is None:
+        out = _like(table, table.shape[0])
+    cnt = (ctypes.c_uint64 * batch)() if count else None
+    cfg = vec_config(is_a_on_device=_is_dev(table), is_result_on_device=_is_dev(out), is_async=is_async, stream=stream,
+                     batch_size=batch)
+    check(lib().mbls_fr_lookup_multiplicities(cols, len(inputs), _p(table), n, bool(montgomery), credit == "last",
+                                              ctypes.byref(cfg), _p(out), cnt), "mbls_fr_lookup_multiplicities")
+    return out, ([int(v) for v in cnt] if count else None)
+
+
+def prefix_sum(col, init=None, inclusive=False, out=None, total=False, *, batch=1, stream=None, is_async=False):
+    """Running sum (mbls_fr_prefix_sum): out[i] = init + sum_{j < i} col[j] per batch member
+    (inclusive: j <= i).  col (batch*n, 4) uint64, numpy (host) or torch (device); init (batch, 4),
+    default zero.  Returns out, a host array unless `out` is a device tensor (`out` may be col);
+    with total=True, or a (batch, 4) buffer placed as `out`, returns (out, total)."""
+    n = col.shape[0] // batch
+    if out is None:
+        out = np.zeros((col.shape[0], 4), dtype=np.uint64)
+    if total is True:
+        total = _like(out, batch)
+    elif total is False:
+        total = None
+    assert total is None or _is_dev(total) == _is_dev(out), "out and total share one placement"
+    cfg = vec_config(is_a_on_device=_is_dev(col), is_b_on_device=_is_dev(init), is_result_on_device=_is_dev(out),
+                     is_async=is_async, stream=stream, batch_size=batch)
+    check(lib().mbls_fr_prefix_sum(_p(col), n, _p(init), bool(inclusive), ctypes.byref(cfg), _p(out), _p(total)),
+          "mbls_fr_prefix_sum")
+    return out if total is None else (out, total)
+
+
+def logup_sum(inputs, table, m, beta, init=None, out=None, total=False, *, batch=1, stream=None, is_async=False):
+    """The log-derivative lookup's running sum (mbls_fr_logup_sum): phi[0] = init, phi[i+1] = phi[i] +
+    sum_c 1 / (inputs[c][i] + beta) - m[i] / (table[i] + beta), 1 / 0 = 0.  inputs, table, m:
+    (batch*n, 4) uint64 Montgomery, all numpy (host) or all torch (device); beta, init (batch, 4),
+    placed alike, init default zero.  Returns phi[0 .. n): `out` when given (it may be m), else a host
+    array; with total=True, or a (batch, 4) buffer placed as `out`, returns (out, total), total =
+    phi[n], zero for a satisfied lookup started from zero."""
+    n = table.shape[0] // batch
+    cols = _column_table(inputs, table)
+    assert m.shape[0] == table.shape[0] and _is_dev(m) == _is_dev(table), "m is sized and placed as the table is"
+    assert init is None or _is_dev(init) == _is_dev(beta), "beta and init share one placement"
+    if out is None:
+        out = np.zeros((table.shape[0], 4), dtype=np.uint64)
+    if total is True:
+        total = _like(out, batch)
+    elif total is False:
+        total = None
+    assert total is None or _is_dev(total) == _is_dev(out), "out and total share one placement"
+    cfg = vec_config(is_a_on_device=_is_dev(table), is_b_on_device=_is_dev(beta), is_result_on_device=_is_dev(out),
+                     is_async=is_async, stream=stream, batch_size=batch)
+    check(lib().mbls_fr_logup_sum(cols, len(inputs), _p(table), _p(m), n, _p(beta), _p(init), ctypes.byref(cfg), _p(out),
+                                  _p(total)), "mbls_fr_logup_sum")
+    return out if total is None else (out, total)
 
 
 # ----------------------------------------------------------------------------- expression evaluator
