@@ -18,25 +18,33 @@
 // measured 3.5x the data bytes fetched by the later passes, profiles/r01.)
 //
 // Kernel structure: ceil(k / MBLS_NTT_PASS_STAGES) = ceil(k / 8) passes of near-equal stage
-// counts, each a LDS-resident tile of T = 2^MBLS_NTT_TILE_LOG = 1024 elements (32 KiB) doing up
-// to 8 radix-2 DIT stages (2^L rows x 2^(10 - L) adjacent columns) between __syncthreads.
-// Pass 1 fuses the bit-reversal permutation into its gather: it reads C adjacent columns of the input viewed
-// as a 2^L x 2^(k-L) matrix (coalesced C*32-byte rows) and writes contiguous DIT blocks.
-// Later passes read/write tiles of 2^L strided rows x C adjacent columns in place.  The
-// inverse's n^-1 scaling is fused into the last pass's store.
+// counts (pass_plan: the one plan every transform here runs and mbls_fr_domain_plan reports), each
+// a LDS-resident tile of T = 2^MBLS_NTT_TILE_LOG = 1024 elements (32 KiB) doing up to 8 radix-2
+// DIT stages (2^L rows x 2^(10 - L) adjacent columns) between __syncthreads.
+// A pass kernel is a load phase, the stage engine, and a store:
+//   tile_stages  the engine, once: the radix-4 stage pairs, the radix-2 tail and the store of a tile
+//                with no stage left, over a tile in LDS, from any first stage; it hands every
+//                finished value to the kernel's put(row, col, v).  The lazy [0, 2r) range argument,
+//                the twiddle indexing and the barrier placement live there and nowhere else.
+//   k_ntt_pass   the plain transform.  Load: pass 1 fuses the bit-reversal permutation into its
+//                gather (C adjacent columns of the input viewed as a 2^L x 2^(k-L) matrix, coalesced
+//                C*32-byte rows, written back as contiguous DIT blocks); later passes read and write
+//                tiles of 2^L strided rows x C adjacent columns in place.  put: the last pass stores
+//                canonical values, the inverse's multiplied by n^-1.  All stages, from l = 1.
+//   k_dom_pass   the first and last passes of the extended-coset transforms of a halo2-style
+//                EvaluationDomain (mbls_fr_coeff_to_extended, mbls_fr_extended_to_coeff; the domain
+//                section at the end of the file).  Load: zero padding, coset scaling and the rows
+//                that stages 1..Ee would only copy, or the vanishing table.  put: the inverse coset
+//                product and the truncated store.  Stages from l = Ee + 1; the passes between its
+//                first and last are k_ntt_pass as it stands.
 // Algorithmic traffic: 64 B per element per transform (one read + one write of 32 B);
 // actual traffic = passes * 64 B + twiddle reads.  Arithmetic: (n/2) log n Montgomery
 // products -- the kernel is VALU-bound on gfx950.
-//
-// The extended-coset transforms of a halo2-style EvaluationDomain (mbls_fr_coeff_to_extended,
-// mbls_fr_extended_to_coeff) live at the end of the file: first and last passes of their own
-// (k_dom_pass) around the passes above.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include <memory>
 #include <mutex>
-#include <type_traits>
 #include <vector>
 
 #include "mbls_common.hpp"
@@ -63,6 +71,17 @@ static constexpr int NTT_PASS_STAGES = MBLS_NTT_PASS_STAGES;
 static const uint64_t ROOT_2_32_MONT[4] = {0xb9b58d8c5f0e466aULL, 0x5b1b4c801819d7ecULL, 0x0af53ae352a31e64ULL,
                                            0x5bf3adda19e9b27bULL};
 
+// the end of a table set (DomainTables, CosetTables): wait for the device that owns it, then free
+static void sync_and_free(int device, void* a, void* b = nullptr) {
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    if (cur != device) (void)hipSetDevice(device);
+    (void)hipDeviceSynchronize();  // every transform that read the tables has finished
+    if (a) (void)hipFree(a);
+    if (b) (void)hipFree(b);
+    if (cur != device) (void)hipSetDevice(cur);
+}
+
 // Twiddle tables of one domain build.  Callers take a shared_ptr snapshot under the lock and
 // enqueue their kernels with it; a table superseded by an extension or a release is freed only
 // when the last snapshot is dropped, and then only after a device synchronisation -- no queued
@@ -76,15 +95,7 @@ struct DomainTables {
     int device = 0;             // device the tables live on
     uint8_t* tw = nullptr;      // per-stage w_(2^s)^i tables (see header)
     uint8_t* tw_inv = nullptr;  // per-stage w_(2^s)^-i
-    ~DomainTables() {
-        int cur = 0;
-        (void)hipGetDevice(&cur);
-        if (cur != device) (void)hipSetDevice(device);
-        (void)hipDeviceSynchronize();  // every transform that read the tables has finished
-        if (tw) (void)hipFree(tw);
-        if (tw_inv) (void)hipFree(tw_inv);
-        if (cur != device) (void)hipSetDevice(cur);
-    }
+    ~DomainTables() { sync_and_free(device, tw, tw_inv); }
 };
 
 // Coset power tables of the extended-coset transforms (see the domain section below): built once
@@ -99,14 +110,7 @@ struct CosetTables {
     uint8_t* mem = nullptr;        // A (2^(log_n - sh) entries) then B (2^sh entries), 32 B each
     const uint4* A = nullptr;      // forward g^(t << sh); inverse N^-1 g^-(t << sh)
     const uint4* B = nullptr;      // forward g^c; inverse g^-c
-    ~CosetTables() {
-        int cur = 0;
-        (void)hipGetDevice(&cur);
-        if (cur != device) (void)hipSetDevice(device);
-        (void)hipDeviceSynchronize();  // every transform that read the tables has finished
-        if (mem) (void)hipFree(mem);
-        if (cur != device) (void)hipSetDevice(cur);
-    }
+    ~CosetTables() { sync_and_free(device, mem); }
 };
 
 struct Domain {
@@ -136,38 +140,44 @@ __device__ __forceinline__ uint32_t bitrev(uint32_t x, int bits) {
 // per-stage tables: entry g (stage s = floor(log2(g+1)) + 1, i = g + 1 - 2^(s-1)) holds
 // w_(2^L)^(i * 2^(L-s)) = w_(2^s)^i, one exponentiation per entry (init only), times 2^5 (the
 // Montgomery form R = 2^256 -> R' = 2^261 of mbls_fr29.hpp), canonical, in the three limb planes
-struct TwPlanes {
-    uint4* a;     // limbs 0-3
-    uint4* b;     // limbs 4-7
-    uint32_t* c;  // limb 8
+template <class Q, class W>
+struct TwPlanesOf {
+    Q* a;  // limbs 0-3
+    Q* b;  // limbs 4-7
+    W* c;  // limb 8
 };
-MBLS_DEV TwPlanes tw_planes(uint8_t* base, uint32_t count) {
-    uint4* a = reinterpret_cast<uint4*>(base);
-    return TwPlanes{a, a + count, reinterpret_cast<uint32_t*>(a + 2 * (size_t)count)};
+using TwPlanes = TwPlanesOf<const uint4, const uint32_t>;  // what the passes read; k_twiddles writes <uint4, uint32_t>
+template <class Q = const uint4, class W = const uint32_t, class B>
+MBLS_DEV TwPlanesOf<Q, W> tw_planes(B* base, uint32_t count) {
+    Q* a = reinterpret_cast<Q*>(base);
+    return {a, a + count, reinterpret_cast<W*>(a + 2 * (size_t)count)};
 }
 static constexpr size_t TW_ENTRY_BYTES = 36;
 // 2^5 R mod r (Montgomery form of 32): x * C32 = x 2^5 (R-form products)
 static constexpr uint32_t TW_C32[8] = {0xffffffbau, 0x00000045u, 0x0072d846u, 0x1a25272eu,
                                        0x5dbeee8bu, 0xfe2eedcdu, 0x9eefbe41u, 0x4d043f42u};
 
-__global__ void k_twiddles(uint8_t* table, Fr w, int L, uint32_t count) {
-    uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= count) return;
-    const int s = 32 - __builtin_clz(g + 1);  // floor(log2(g+1)) + 1
-    const uint32_t i = g + 1 - (1u << (s - 1));
+// b^e by square and multiply (table builds and the coset scaling: one ladder per entry)
+MBLS_DEV Fr fr_pow(Fr b, uint64_t e) {
     Fr acc = Fr::one();
-    Fr b = w;
-    uint64_t e = (uint64_t)i << (L - s);
     while (e) {
         if (e & 1) acc = acc * b;
         b = sqr(b);
         e >>= 1;
     }
+    return acc;
+}
+
+__global__ void k_twiddles(uint8_t* table, Fr w, int L, uint32_t count) {
+    uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= count) return;
+    const int s = 32 - __builtin_clz(g + 1);  // floor(log2(g+1)) + 1
+    const uint32_t i = g + 1 - (1u << (s - 1));
     Fr c32;
 #pragma unroll
     for (int k = 0; k < 8; ++k) c32.v[k] = TW_C32[k];
-    const r29::F29 t = r29::unpack(acc * c32);  // w R' mod r, canonical
-    const TwPlanes P = tw_planes(table, count);
+    const r29::F29 t = r29::unpack(fr_pow(w, (uint64_t)i << (L - s)) * c32);  // w R' mod r, canonical
+    const auto P = tw_planes<uint4, uint32_t>(table, count);
     P.a[g] = make_uint4(t.l[0], t.l[1], t.l[2], t.l[3]);
     P.b[g] = make_uint4(t.l[4], t.l[5], t.l[6], t.l[7]);
     P.c[g] = t.l[8];
@@ -214,12 +224,152 @@ MBLS_DEV void st2(uint4* p, uint32_t e, const Fr& v) {
     p[2 * e + 1] = make_uint4(v.v[4], v.v[5], v.v[6], v.v[7]);
 }
 // twiddle entry g of the limb planes
-MBLS_DEV r29::F29 ldtw(const uint4* a, const uint4* b, const uint32_t* c, uint32_t g) {
-    const uint4 x = a[g], y = b[g];
-    return r29::F29{{x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w, c[g]}};
+MBLS_DEV r29::F29 ldtw(const TwPlanes& P, uint32_t g) {
+    const uint4 x = P.a[g], y = P.b[g];
+    return r29::F29{{x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w, P.c[g]}};
 }
 
-// One pass of up to NTT_TILE_LOG DIT stages.
+// Where a pass's tile lies.  A first pass views the polynomial as 2^L rows x 2^colbits columns and
+// takes C adjacent columns from lo0: element (row t, column c) at (t << colbits) + lo0 + c, written
+// back as contiguous DIT blocks.  A later pass works in place on 2^L rows 2^s0 apart: element (t, c)
+// at hi_base + (t << s0) + lo0 + c.
+struct Tile {
+    uint32_t poly;  // batch member
+    uint32_t lo0, hi_base;
+};
+template <bool FIRST>
+MBLS_DEV Tile tile_of(uint32_t id, int log_n, int s0, int L, int logC) {
+    const uint32_t tiles_per_poly = (uint32_t)(((size_t)1 << log_n) >> (L + logC));
+    const uint32_t lo_tiles = FIRST ? 1u : (1u << s0) >> logC;
+    const uint32_t poly = id / tiles_per_poly, tile = id % tiles_per_poly;
+    return Tile{poly, (FIRST ? tile : tile % lo_tiles) << logC, FIRST ? 0u : (tile / lo_tiles) << (s0 + L)};
+}
+// ... and where its finished value (row, c) goes
+template <bool FIRST>
+MBLS_DEV uint32_t tile_dst(const Tile& g, uint32_t row, uint32_t c, int log_n, int s0, int L) {
+    return FIRST ? (bitrev(g.lo0 + c, log_n - L) << L) + row : g.hi_base + (row << s0) + g.lo0 + c;
+}
+
+// The stage engine both pass kernels run: stages l0..L of a pass (global stages s0 + l0 .. s0 + L)
+// over a tile of 2^L rows x 2^logC columns that lies in LDS as [row][col], rows in DIT order, and
+// behind a barrier.  Pairs of stages run as radix-4 (2 x 2) butterflies in registers (one LDS round
+// trip and one barrier per pair), an odd last stage as radix-2.  The last stage group hands every
+// finished value, still in [0, 2r), to put(row, col, v) straight from registers: no LDS round
+// trip, barrier or separate store loop; with no stage to run (l0 > L) the tile itself is handed over.
+//
+// TRIV is how the first pair of a first pass (l = 1: j = 0, every twiddle but one is 1) skips its
+// three products.  Each kernel keeps its own treatment of that pair, behind this one parameter,
+// because both sit within a few registers of the limit of 5 waves per SIMD and the register
+// allocation follows the form of the source (profiles/ntt_engine/kernels_cmp.txt):
+//   from_l  one loop body that decides from l at run time: k_ntt_pass.  Peeled, its first passes
+//           grow by a third (2288 -> 3003 instructions for <true, false, false>).
+//   peeled  the pair at l = 1 gets a body of its own (always), the others one without the test
+//           (never): k_dom_pass.  Deciding at run time, its first passes spill (0 -> 4 registers for
+//           <true, false, *>, 1 -> 26 for <true, true, true>).
+// Which of the two would be faster for the plain first pass is a question of its own.
+enum class TrivPair { from_l, peeled };  // what a kernel asks of tile_stages
+enum class Triv { from_l, always, never };  // what tile_stages asks of one stage pair
+
+// stages l, l + 1 of the tile; fin: no stage follows, the outputs go to put
+template <bool FIRST, Triv TRIV, class Put>
+MBLS_DEV void stage_pair(uint4* lds, const TwPlanes& tw, int l, int s0, int L, int logC, uint32_t lo_base,
+                         const Put& put) {
+    const uint32_t C = 1u << logC, T = C << L;
+    const bool fin = l + 2 > L;
+    const uint32_t h = 1u << (l - 1);  // stage l pairs rows (t, t + h), stage l + 1 rows (t, t + 2h)
+    const int s = s0 + l;              // global stage of the first of the pair
+    const uint32_t t1 = (1u << (s - 1)) - 1, t2 = (1u << s) - 1;  // stage tables s, s + 1
+    const uint32_t stride = h * C;
+    for (uint32_t u = threadIdx.x; u < T / 4; u += NTT_THREADS) {
+        const uint32_t c = u & (C - 1);
+        const uint32_t r = u >> logC;
+        const uint32_t j = r & (h - 1);
+        const uint32_t q = ((r >> (l - 1)) << (l + 1)) + j;
+        const uint32_t e0 = q * C + c;
+        const uint32_t lo = FIRST ? 0u : lo_base + c;
+        const bool triv = TRIV == Triv::from_l ? FIRST && l == 1 : TRIV == Triv::always;
+        // twiddles first: their loads do not depend on the tile
+        r29::F29 w1, w2, w3;
+        const uint32_t jl = (j << s0) + lo;
+        if (!triv) {
+            w1 = ldtw(tw, t1 + jl);
+            w2 = ldtw(tw, t2 + jl);
+        }
+        w3 = ldtw(tw, t2 + jl + (h << s0));
+        Fr x0 = ld2(lds, e0), x1 = ld2(lds, e0 + stride), x2 = ld2(lds, e0 + 2 * stride),
+           x3 = ld2(lds, e0 + 3 * stride);
+        // stage l: (x0, x1), (x2, x3) share twiddle w_(2^s)^j
+        if (!triv) {
+            x1 = r29::mul_words(x1, w1);
+            x3 = r29::mul_words(x3, w1);
+        }
+        Fr y0 = add_2r(x0, x1), y1 = sub_2r(x0, x1), y2 = add_2r(x2, x3), y3 = sub_2r(x2, x3);
+        // stage l + 1: (y0, y2) with w_(2^(s+1))^j, (y1, y3) with w_(2^(s+1))^(j + h)
+        if (!triv) y2 = r29::mul_words(y2, w2);
+        y3 = r29::mul_words(y3, w3);
+        if (fin) {
+            put(q, c, add_2r(y0, y2));
+            put(q + 2 * h, c, sub_2r(y0, y2));
+            put(q + h, c, add_2r(y1, y3));
+            put(q + 3 * h, c, sub_2r(y1, y3));
+        } else {
+            st2(lds, e0, add_2r(y0, y2));
+            st2(lds, e0 + 2 * stride, sub_2r(y0, y2));
+            st2(lds, e0 + stride, add_2r(y1, y3));
+            st2(lds, e0 + 3 * stride, sub_2r(y1, y3));
+        }
+    }
+}
+
+template <bool FIRST, TrivPair TRIV, class Put>
+MBLS_DEV void tile_stages(uint4* lds, const uint8_t* tw_, uint32_t tw_count, int l0, int s0, int L, int logC,
+                          uint32_t lo0, const Put& put) {
+    const TwPlanes tw = tw_planes(tw_, tw_count);
+    const uint32_t C = 1u << logC, T = C << L;
+    const uint32_t lo_base = FIRST ? 0u : lo0;
+    int l = l0;
+    for (; l + 1 <= L; l += 2) {
+        if constexpr (TRIV == TrivPair::from_l) stage_pair<FIRST, Triv::from_l>(lds, tw, l, s0, L, logC, lo_base, put);
+        else if (FIRST && l == 1) stage_pair<FIRST, Triv::always>(lds, tw, l, s0, L, logC, lo_base, put);
+        else stage_pair<FIRST, Triv::never>(lds, tw, l, s0, L, logC, lo_base, put);
+        if (l + 2 > L) return;
+        __syncthreads();
+    }
+    if (l == L) {  // one radix-2 stage left
+        const uint32_t half = 1u << (l - 1);
+        const int s = s0 + l;                     // global stage, m = 2^s
+        const uint32_t ts = (1u << (s - 1)) - 1;  // stage table s
+        for (uint32_t u = threadIdx.x; u < T / 2; u += NTT_THREADS) {
+            const uint32_t c = u & (C - 1);
+            const uint32_t r = u >> logC;
+            const uint32_t gg = r >> (l - 1);
+            const uint32_t j = r & (half - 1);
+            const uint32_t t0 = (gg << l) + j, t1 = t0 + half;
+            r29::F29 w;  // a lone first stage of a first pass has twiddle 1
+            if (l > 1 || !FIRST) w = ldtw(tw, ts + (j << s0) + (FIRST ? 0u : lo_base + c));
+            const Fr a = ld2(lds, t0 * C + c);
+            Fr b = ld2(lds, t1 * C + c);
+            if (l > 1 || !FIRST) b = r29::mul_words(b, w);
+            put(t0, c, add_2r(a, b));
+            put(t1, c, sub_2r(a, b));
+        }
+        return;
+    }
+    // ---- no stage to run (L == 0, or a first pass whose stages were all replication)
+    for (uint32_t e = threadIdx.x; e < T; e += NTT_THREADS) {
+        if (FIRST) {
+            // block by block: consecutive threads -> consecutive positions of one output block
+            const uint32_t p = e & ((1u << L) - 1), c = e >> L;
+            put(p, c, ld2(lds, p * C + c));
+        } else {
+            const uint32_t c = e & (C - 1), t = e >> logC;
+            put(t, c, ld2(lds, e));
+        }
+    }
+}
+
+// One pass of up to NTT_TILE_LOG DIT stages of the plain transform: the load phase and the store
+// (put) here, the stages in tile_stages.
 //   FIRST: stages 1..L with the bit-reversal gather from `in`; else stages s0+1..s0+L in place.
 //   LAST:  store canonical values; SCALE (inverse, implies LAST): multiply them by n^-1.
 // One tile per workgroup, grid = tiles.  Persistent workgroups walking several tiles lost in every
@@ -239,146 +389,29 @@ __global__ __launch_bounds__(NTT_THREADS, 5) void k_ntt_pass(uint8_t* __restrict
                                                                          int logC, Fr scale, uint32_t ntiles) {
     __shared__ uint4 lds[NTT_TILE * 2];
     const uint32_t C = 1u << logC;
-    const uint32_t rows = 1u << L;
-    const uint32_t T = rows * C;  // active tile elements (== NTT_TILE except for tiny transforms)
-    const size_t n = (size_t)1 << log_n;
-    const uint32_t tiles_per_poly = (uint32_t)(n >> (L + logC));
-    // twiddle limb planes (k_twiddles)
-    const uint4* twa = reinterpret_cast<const uint4*>(tw_);
-    const uint4* twb = twa + tw_count;
-    const uint32_t* twc = reinterpret_cast<const uint32_t*>(twa + 2 * (size_t)tw_count);
-    // FIRST: element (row tr, column c0 + c) at (tr << colbits) + c0 + c; else element (t, c) at
-    // hi_base + (t << s0) + lo0 + c
+    const uint32_t T = C << L;  // active tile elements (== NTT_TILE except for tiny transforms)
     const uint32_t colbits = (uint32_t)(log_n - L);
-    const uint32_t lo_tiles = FIRST ? 1u : (1u << s0) >> logC;
-    struct Tile {
-        size_t poly;  // element offset of the tile's polynomial
-        uint32_t lo0, hi_base;
-    };
-    auto tile_of = [&](uint32_t id) {
-        const uint32_t poly = id / tiles_per_poly, tile = id % tiles_per_poly;
-        return Tile{(size_t)poly * n, FIRST ? tile * C : (tile % lo_tiles) * C,
-                    FIRST ? 0u : (tile / lo_tiles) << (s0 + L)};
-    };
-    // element e of the tile ([row t][col c] in LDS order): its index in the polynomial
-    auto src_of = [&](const Tile& g, uint32_t e) {
-        const uint32_t c = e & (C - 1), t = e >> logC;
-        return FIRST ? (t << colbits) + g.lo0 + c : g.hi_base + (t << s0) + g.lo0 + c;
-    };
-    const uint4* in = reinterpret_cast<const uint4*>(FIRST ? in_ : out_);
-    uint4* out = reinterpret_cast<uint4*>(out_);
-
     const uint32_t id = blockIdx.x;  // one tile per workgroup
     if (id >= ntiles) return;
-    const Tile g = tile_of(id);
-    {
-        // ---- the tile into LDS as [row t][col c] (FIRST: rows at their bit-reversed DIT
-        // position; not vectorised: the loop vectoriser split the b128 LDS stores into b32)
+    const Tile g = tile_of<FIRST>(id, log_n, s0, L, logC);
+    const size_t poly = (size_t)g.poly << log_n;  // element offset of the tile's polynomial
+    const uint4* in = reinterpret_cast<const uint4*>(FIRST ? in_ : out_);
+    uint4* o = reinterpret_cast<uint4*>(out_) + 2 * poly;
+    // ---- the tile into LDS as [row t][col c] (FIRST: rows at their bit-reversed DIT position; not
+    // vectorised: the loop vectoriser split the b128 LDS stores into b32)
 #pragma clang loop vectorize(disable) interleave(disable)
-        for (uint32_t e = threadIdx.x; e < T; e += NTT_THREADS) {
-            const uint32_t c = e & (C - 1), t = e >> logC;
-            st2(lds, FIRST ? bitrev(t, L) * C + c : e, ld2(in + 2 * g.poly, src_of(g, e)));
-        }
-        __syncthreads();
-        // ---- L DIT stages: pairs of stages as radix-4 (2 x 2) butterflies in registers (one LDS
-        // round trip and one barrier per pair), an odd last stage as radix-2
-        const uint32_t lo_base = FIRST ? 0u : g.lo0;
-        uint4* o = out + 2 * g.poly;
-        // the last stage group stores its outputs straight to HBM from registers:
-        // no LDS round trip, barrier or separate store loop; (row, c) of the tile -> its position
-        auto put = [&](uint32_t row, uint32_t c, Fr v) {
-            if (SCALE) v = v * scale;  // v < 2r, scale < r: the reduced product is canonical
-            else if (LAST) reduce_once(v);
-            st2(o, FIRST ? (bitrev(g.lo0 + c, colbits) << L) + row : g.hi_base + (row << s0) + g.lo0 + c, v);
-        };
-        int l = 1;
-        for (; l + 1 <= L; l += 2) {
-            const bool fin = l + 2 > L;  // the last pair, no radix-2 stage after it
-            const uint32_t h = 1u << (l - 1);  // stage l pairs rows (t, t + h), stage l + 1 rows (t, t + 2h)
-            const int s = s0 + l;              // global stage of the first of the pair
-            const uint32_t t1 = (1u << (s - 1)) - 1, t2 = (1u << s) - 1;  // stage tables s, s + 1
-            const uint32_t stride = h * C;
-            for (uint32_t u = threadIdx.x; u < T / 4; u += NTT_THREADS) {
-                const uint32_t c = u & (C - 1);
-                const uint32_t r = u >> logC;
-                const uint32_t j = r & (h - 1);
-                const uint32_t q = ((r >> (l - 1)) << (l + 1)) + j;
-                const uint32_t e0 = q * C + c;
-                const uint32_t lo = FIRST ? 0u : lo_base + c;
-                const bool triv = FIRST && l == 1;  // first pair of the first pass: j = 0, twiddles 1
-                // twiddles first: their loads do not depend on the tile
-                r29::F29 w1, w2, w3;
-                const uint32_t jl = (j << s0) + lo;
-                if (!triv) {
-                    w1 = ldtw(twa, twb, twc, t1 + jl);
-                    w2 = ldtw(twa, twb, twc, t2 + jl);
-                }
-                w3 = ldtw(twa, twb, twc, t2 + jl + (h << s0));
-                Fr x0 = ld2(lds, e0), x1 = ld2(lds, e0 + stride), x2 = ld2(lds, e0 + 2 * stride),
-                   x3 = ld2(lds, e0 + 3 * stride);
-                // stage l: (x0, x1), (x2, x3) share twiddle w_(2^s)^j
-                if (!triv) {
-                    x1 = r29::mul_words(x1, w1);
-                    x3 = r29::mul_words(x3, w1);
-                }
-                Fr y0 = add_2r(x0, x1), y1 = sub_2r(x0, x1), y2 = add_2r(x2, x3), y3 = sub_2r(x2, x3);
-                // stage l + 1: (y0, y2) with w_(2^(s+1))^j, (y1, y3) with w_(2^(s+1))^(j + h)
-                if (!triv) y2 = r29::mul_words(y2, w2);
-                y3 = r29::mul_words(y3, w3);
-                if (fin) {
-                    put(q, c, add_2r(y0, y2));
-                    put(q + 2 * h, c, sub_2r(y0, y2));
-                    put(q + h, c, add_2r(y1, y3));
-                    put(q + 3 * h, c, sub_2r(y1, y3));
-                } else {
-                    st2(lds, e0, add_2r(y0, y2));
-                    st2(lds, e0 + 2 * stride, sub_2r(y0, y2));
-                    st2(lds, e0 + stride, add_2r(y1, y3));
-                    st2(lds, e0 + 3 * stride, sub_2r(y1, y3));
-                }
-            }
-            if (fin) return;
-            __syncthreads();
-        }
-        if (l == L) {  // odd stage count: one radix-2 stage
-            const uint32_t half = 1u << (l - 1);
-            const int s = s0 + l;                     // global stage, m = 2^s
-            const uint32_t ts = (1u << (s - 1)) - 1;  // stage table s
-            for (uint32_t u = threadIdx.x; u < T / 2; u += NTT_THREADS) {
-                const uint32_t c = u & (C - 1);
-                const uint32_t r = u >> logC;
-                const uint32_t gg = r >> (l - 1);
-                const uint32_t j = r & (half - 1);
-                const uint32_t t0 = (gg << l) + j, t1 = t0 + half;
-                r29::F29 w;
-                if (l > 1 || !FIRST) w = ldtw(twa, twb, twc, ts + (j << s0) + (FIRST ? 0u : lo_base + c));
-                const Fr a = ld2(lds, t0 * C + c);
-                Fr b = ld2(lds, t1 * C + c);
-                if (l > 1 || !FIRST) b = r29::mul_words(b, w);
-                put(t0, c, add_2r(a, b));
-                put(t1, c, sub_2r(a, b));
-            }
-            return;
-        }
-
-        // ---- store (a pass with L = 0 only: every stage group above returns)
-        for (uint32_t e = threadIdx.x; e < T; e += NTT_THREADS) {
-            Fr v;
-            uint32_t dst;
-            if (FIRST) {
-                // write block by block: consecutive threads -> consecutive positions of one block
-                const uint32_t p = e & (rows - 1), c = e >> L;
-                v = ld2(lds, p * C + c);
-                dst = (bitrev(g.lo0 + c, colbits) << L) + p;
-            } else {
-                v = ld2(lds, e);
-                dst = src_of(g, e);
-            }
-            if (SCALE) v = v * scale;  // v < 2r, scale < r: the reduced product is canonical
-            else if (LAST) reduce_once(v);
-            st2(o, dst, v);
-        }
+    for (uint32_t e = threadIdx.x; e < T; e += NTT_THREADS) {
+        const uint32_t c = e & (C - 1), t = e >> logC;
+        st2(lds, FIRST ? bitrev(t, L) * C + c : e,
+            ld2(in + 2 * poly, FIRST ? (t << colbits) + g.lo0 + c : g.hi_base + (t << s0) + g.lo0 + c));
     }
+    __syncthreads();
+    auto put = [&](uint32_t row, uint32_t c, Fr v) {
+        if (SCALE) v = v * scale;  // v < 2r, scale < r: the reduced product is canonical
+        else if (LAST) reduce_once(v);
+        st2(o, tile_dst<FIRST>(g, row, c, log_n, s0, L), v);
+    };
+    tile_stages<FIRST, TrivPair::from_l>(lds, tw_, tw_count, 1, s0, L, logC, g.lo0, put);
 }
 
 __global__ void k_copy_scale(uint8_t* out, const uint8_t* in, size_t count, Fr scale, int do_scale) {
@@ -512,59 +545,120 @@ static eIcicleError build_domain(Domain& dom, int max_log, hipStream_t st, std::
     return MBLS_SUCCESS;
 }
 
+// The domain as one call sees it: under the lock, bound the size by the initialised root's order,
+// build or extend this device's stage tables when they are too short (init_domain builds up to
+// 2^22), and snapshot them; the snapshot stays valid for the whole enqueue.  `superseded` takes an
+// extension's old tables: the caller lets it go outside the lock (build_domain).
+struct CosetWant {  // the coset tables a domain transform takes under the same lock (coset_tables)
+    const uint64_t* g;
+    int sh;
+    bool inverse;
+    std::shared_ptr<CosetTables> got, evicted;  // evicted: let go outside the lock, as superseded
+};
+static eIcicleError coset_tables(Domain& dom, int log_n, hipStream_t st, CosetWant& w);
+static eIcicleError domain_snapshot(int log_n, hipStream_t st, std::shared_ptr<DomainTables>& tables,
+                                    std::shared_ptr<DomainTables>& superseded, CosetWant* coset = nullptr) {
+    std::lock_guard<std::mutex> lk(g_domain_mu);
+    Domain* dom = current_domain();
+    if (!dom) return MBLS_INVALID_DEVICE;
+    if (log_n > dom->order_log) return MBLS_INVALID_ARGUMENT;  // beyond the initialised root
+    if (!dom->tables || dom->tables->max_log < log_n) {
+        int want = log_n < 20 ? 20 : log_n;
+        if (want > dom->order_log) want = dom->order_log;
+        eIcicleError er = build_domain(*dom, want, st, superseded);
+        if (er != MBLS_SUCCESS) return er;
+    }
+    tables = dom->tables;
+    return coset ? coset_tables(*dom, log_n, st, *coset) : MBLS_SUCCESS;
+}
+
+// n^-1 for n = 2^log_n, Montgomery form
+static void hfr_ninv(uint64_t* r, int log_n) {
+    uint64_t nm[4] = {(uint64_t)1 << log_n, 0, 0, 0};
+    hfr_mul(nm, nm, HFR_R2);  // n in Montgomery form
+    hfr_inv(r, nm);
+}
+
+// A caller's coset generator into g: 1 a coset, 0 none (no generator, or 1), -1 not a generator --
+// zero mod r (a zero-initialised NTTConfig) has no inverse and spans no coset
+static int coset_kind(const mbls_fr_t* coset_gen, uint64_t* g) {
+    if (!coset_gen) return 0;
+    memcpy(g, coset_gen->limbs, 32);
+    uint64_t gr[4];
+    hfr_mul(gr, g, HFR_R2);  // g R mod r, canonical for any 256-bit g
+    const uint64_t zero[4] = {0, 0, 0, 0};
+    if (hfr_eq(gr, zero)) return -1;
+    return hfr_eq(g, HFR_ONE) ? 0 : 1;
+}
+
+static constexpr int NTT_MAX_LOG = 30;    // sizes are ints, element indices 32-bit
+static constexpr int NTT_MAX_PASSES = 4;  // ceil(30 / 8)
+
+// a pass's grid: tiles per polynomial times batch members (below 2^31 for every pass pass_plan returns)
+static size_t pass_tiles(int log_n, int L, int logC, int batch) {
+    return (((size_t)1 << log_n) >> (L + logC)) * (size_t)batch;
+}
+
+// The pass plan of a transform of 2^log_n, (s0, L, logC) per pass: the log_n stages split into
+// ceil(log_n / NTT_PASS_STAGES) passes of near-equal stage counts L (tile rows 2^L), each tile with
+// as many adjacent columns 2^logC as the tile size and the available column count allow (8 stages
+// leave >= 4 columns: >= 128-byte contiguous row segments in HBM).  Returns the pass count (0 for
+// log_n == 0), or -1 where a pass's tile count times `batch`, its grid, would reach 2^31.
+static int pass_plan(int log_n, int batch, int (*pl)[3]) {
+    const int npass = (log_n + NTT_PASS_STAGES - 1) / NTT_PASS_STAGES;
+    int s0 = 0;
+    for (int p = 0; p < npass; ++p) {
+        const int remaining = log_n - s0;
+        const int L = (remaining + (npass - p) - 1) / (npass - p);
+        const int colspace = p == 0 ? (log_n - L) : s0;
+        int logC = NTT_TILE_LOG - L;
+        if (logC > colspace) logC = colspace;
+        if (pass_tiles(log_n, L, logC, batch) > 0x7fffffff) return -1;
+        pl[p][0] = s0, pl[p][1] = L, pl[p][2] = logC;
+        s0 += L;
+    }
+    return npass;
+}
+
+// one k_ntt_pass over `batch` polynomials of 2^log_n in `out` (a first pass gathers from `in`)
+static eIcicleError launch_ntt_pass(bool first, bool last, bool inverse, uint8_t* out, const uint8_t* in,
+                                    const uint8_t* tw, uint32_t tw_count, int log_n, const int* pl, Fr scale, int batch,
+                                    hipStream_t st) {
+    const int s0 = pl[0], L = pl[1], logC = pl[2];
+    const uint32_t nt = (uint32_t)pass_tiles(log_n, L, logC, batch);
+    auto* k = k_ntt_pass<false, false, false>;
+    if (first && last) k = inverse ? k_ntt_pass<true, true, true> : k_ntt_pass<true, true, false>;
+    else if (first) k = k_ntt_pass<true, false, false>;
+    else if (last) k = inverse ? k_ntt_pass<false, true, true> : k_ntt_pass<false, true, false>;
+    hipLaunchKernelGGL(k, dim3(nt), dim3(NTT_THREADS), 0, st, out, in, tw, tw_count, log_n, s0, L, logC, scale, nt);
+    MBLS_TRY(hipGetLastError());
+    return MBLS_SUCCESS;
+}
+
 // enqueue forward/inverse NTT of `batch` polynomials of 2^log_n on device buffers
 // (D: the caller's snapshot of the domain tables, kept alive across the enqueue)
 eIcicleError ntt_device(uint8_t* out, const uint8_t* in, int log_n, bool inverse, int batch, const DomainTables& D,
                         hipStream_t st) {
-    if (!D.tw || log_n > D.max_log) return MBLS_INVALID_ARGUMENT;
-    const size_t n = (size_t)1 << log_n;
-    const uint8_t* tw = inverse ? D.tw_inv : D.tw;
-    uint64_t ninv_h[4] = {0, 0, 0, 0};
-    if (inverse) {
-        uint64_t nm[4] = {n, 0, 0, 0};
-        hfr_mul(nm, nm, HFR_R2);  // n in Montgomery form
-        hfr_inv(ninv_h, nm);
-    }
-    Fr scale = to_dev(inverse ? ninv_h : HFR_ONE);
-    if (log_n == 0) {
+    if (!D.tw || log_n > D.max_log || log_n > NTT_MAX_LOG) return MBLS_INVALID_ARGUMENT;
+    int pl[NTT_MAX_PASSES][3];
+    const int np = pass_plan(log_n, batch, pl);
+    if (np < 0) return MBLS_INVALID_ARGUMENT;
+    uint64_t ninv_h[4];
+    memcpy(ninv_h, HFR_ONE, 32);
+    if (inverse) hfr_ninv(ninv_h, log_n);
+    const Fr scale = to_dev(ninv_h);
+    if (np == 0) {
         size_t cnt = (size_t)batch;
         hipLaunchKernelGGL(k_copy_scale, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, out, in, cnt, scale, 0);
         MBLS_TRY(hipGetLastError());
         return MBLS_SUCCESS;
     }
-    // split the k stages into passes of <= NTT_PASS_STAGES stages (tile rows), so that a tile
-    // keeps >= 4 adjacent columns (>= 128-byte contiguous row segments in HBM)
-    int npass = (log_n + NTT_PASS_STAGES - 1) / NTT_PASS_STAGES;
-    int s0 = 0;
     ProfScope prof_t("ntt.transform", st);
-    for (int p = 0; p < npass; ++p) {
+    for (int p = 0; p < np; ++p) {
         ProfScope prof_p("ntt.pass", st);
-        int remaining = log_n - s0;
-        int L = (remaining + (npass - p) - 1) / (npass - p);
-        bool first = (p == 0);
-        bool last = (p == npass - 1);
-        // columns per tile: limited by the tile size and by the available column count
-        int colspace = first ? (log_n - L) : s0;
-        int logC = NTT_TILE_LOG - L;
-        if (logC > colspace) logC = colspace;
-        size_t tiles = (n >> (L + logC)) * (size_t)batch;
-        if (tiles > 0x7fffffff) return MBLS_INVALID_ARGUMENT;
-        const uint32_t nt = (uint32_t)tiles;
-        dim3 grid(nt), blk(NTT_THREADS);
-        if (first && last && inverse)
-            hipLaunchKernelGGL((k_ntt_pass<true, true, true>), grid, blk, 0, st, out, in, tw, D.count, log_n, s0, L, logC, scale, nt);
-        else if (first && last)
-            hipLaunchKernelGGL((k_ntt_pass<true, true, false>), grid, blk, 0, st, out, in, tw, D.count, log_n, s0, L, logC, scale, nt);
-        else if (first)
-            hipLaunchKernelGGL((k_ntt_pass<true, false, false>), grid, blk, 0, st, out, in, tw, D.count, log_n, s0, L, logC, scale, nt);
-        else if (last && inverse)
-            hipLaunchKernelGGL((k_ntt_pass<false, true, true>), grid, blk, 0, st, out, in, tw, D.count, log_n, s0, L, logC, scale, nt);
-        else if (last)
-            hipLaunchKernelGGL((k_ntt_pass<false, true, false>), grid, blk, 0, st, out, in, tw, D.count, log_n, s0, L, logC, scale, nt);
-        else
-            hipLaunchKernelGGL((k_ntt_pass<false, false, false>), grid, blk, 0, st, out, in, tw, D.count, log_n, s0, L, logC, scale, nt);
-        MBLS_TRY(hipGetLastError());
-        s0 += L;
+        const eIcicleError er = launch_ntt_pass(p == 0, p == np - 1, inverse, out, in, inverse ? D.tw_inv : D.tw, D.count,
+                                                log_n, pl[p], scale, batch, st);
+        if (er != MBLS_SUCCESS) return er;
     }
     return MBLS_SUCCESS;
 }
@@ -617,15 +711,8 @@ eIcicleError ntt_release_domain() {
 __global__ void k_coset_scale(uint8_t* data, Fr g, size_t n, size_t total) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i >= total) return;
-    size_t e = i & (n - 1);
-    Fr acc = Fr::one(), b = g;
-    while (e) {
-        if (e & 1) acc = acc * b;
-        b = sqr(b);
-        e >>= 1;
-    }
     Fr v = load<FrCfg>(data + 32 * i);
-    store<FrCfg>(data + 32 * i, v * acc);
+    store<FrCfg>(data + 32 * i, v * fr_pow(g, i & (n - 1)));
 }
 
 // Layout permutation (gather): out position q of layout (out_cols, out_rev) takes the element
@@ -667,39 +754,19 @@ eIcicleError ntt_call(const mbls_fr_t* input, int size, NTTDir dir, const NTTCon
     if (log_n < 0) return MBLS_INVALID_ARGUMENT;
     const int ord = (int)cfg->ordering;
     if (ord < MBLS_ORDERING_NN || ord > MBLS_ORDERING_MN) return MBLS_INVALID_ARGUMENT;
-    // coset: forward evaluates on g*H (pre-scale by g^i); inverse post-scales by g^-i.  A generator
-    // that is zero mod r (a zero-initialised NTTConfig) has no inverse and spans no coset
-    bool coset = false;
+    // coset: forward evaluates on g*H (pre-scale by g^i); inverse post-scales by g^-i
     uint64_t g[4];
-    if (coset_gen) {
-        memcpy(g, coset_gen->limbs, 32);
-        uint64_t gr[4];
-        hfr_mul(gr, g, HFR_R2);  // g R mod r, canonical for any 256-bit g
-        const uint64_t zero[4] = {0, 0, 0, 0};
-        if (hfr_eq(gr, zero)) return MBLS_INVALID_ARGUMENT;
-        coset = !hfr_eq(g, HFR_ONE);
-    }
+    const int kind = coset_kind(coset_gen, g);
+    if (kind < 0) return MBLS_INVALID_ARGUMENT;
+    const bool coset = kind > 0;
     const bool in_rev = ord == MBLS_ORDERING_RN || ord == MBLS_ORDERING_RR || ord == MBLS_ORDERING_MN;
     const bool out_rev = ord == MBLS_ORDERING_NR || ord == MBLS_ORDERING_RR || ord == MBLS_ORDERING_NM;
     const bool cols = cfg->columns_batch;
     int batch = cfg->batch_size > 0 ? cfg->batch_size : 1;
     hipStream_t st = static_cast<hipStream_t>(cfg->stream);
-    std::shared_ptr<DomainTables> tables;  // snapshot: valid for the whole enqueue below
-    std::shared_ptr<DomainTables> superseded;  // an extension's old tables, dropped outside the lock
-    {
-        std::lock_guard<std::mutex> lk(g_domain_mu);
-        Domain* dom = current_domain();
-        if (!dom) return MBLS_INVALID_DEVICE;
-        if (log_n > dom->order_log) return MBLS_INVALID_ARGUMENT;  // beyond the initialised root
-        if (!dom->tables || dom->tables->max_log < log_n) {
-            // lazily build / extend this device's stage tables (init_domain builds up to 2^22)
-            int want = log_n < 20 ? 20 : log_n;
-            if (want > dom->order_log) want = dom->order_log;
-            eIcicleError er = build_domain(*dom, want, st, superseded);
-            if (er != MBLS_SUCCESS) return er;
-        }
-        tables = dom->tables;
-    }
+    std::shared_ptr<DomainTables> tables, superseded;
+    eIcicleError er = domain_snapshot(log_n, st, tables, superseded);
+    if (er != MBLS_SUCCESS) return er;
     const size_t bytes = (size_t)size * 32 * (size_t)batch;
     const size_t total = (size_t)size * batch;
     const bool inverse = (dir == MBLS_NTT_INVERSE);
@@ -721,8 +788,7 @@ eIcicleError ntt_call(const mbls_fr_t* input, int size, NTTDir dir, const NTTCon
     S.out(&dst, output, bytes, out_dev);
     if (perm_out) S.scratch(&wout, bytes);
     if (work_in_tmp) S.scratch(&t, bytes);
-    eIcicleError er = S.open();
-    if (er != MBLS_SUCCESS) return er;
+    if ((er = S.open()) != MBLS_SUCCESS) return er;
     if (!perm_out) wout = dst;
     const uint8_t* win = src;
     if (work_in_tmp) {
@@ -765,17 +831,17 @@ eIcicleError ntt_domain_roots(int log_n, bool inverse, uint64_t* w, uint64_t* n_
     }
     canonical_omega(w, log_n);
     if (inverse) hfr_inv(w, w);
-    uint64_t nm[4] = {(uint64_t)1 << log_n, 0, 0, 0};
-    hfr_mul(nm, nm, HFR_R2);  // n in Montgomery form
-    hfr_inv(n_inv, nm);
+    hfr_ninv(n_inv, log_n);
     return MBLS_SUCCESS;
 }
 bool fr_is_montgomery_one(const uint64_t* a) { return hfr_eq(a, HFR_ONE); }
 
 // ---------------------------------------------------------------------------------------------
 // Extended-coset transforms: halo2's EvaluationDomain::coeff_to_extended and extended_to_coeff
-// (DESIGN.md 5.12).  Same pass plan, tiles, twiddles and butterflies as ntt_device; the first and
-// last passes are k_dom_pass, the passes between them are k_ntt_pass<false, ...> as they stand.
+// (DESIGN.md 5.12).  The plan (pass_plan), the tiles, the twiddles and the stage engine (tile_stages)
+// are the plain transform's.  k_dom_pass adds what the first and the last pass do differently -- its
+// own load phase, a first stage past the replicated ones, and its own put -- and the passes between
+// them are k_ntt_pass<false, ...> as they stand (launch_ntt_pass).
 //
 // Forward (size coefficients -> N = 2^K values on g H_N), E = K - log2(next_pow2(size)):
 //   the first pass's tile rows are the indices (t << colbits) + col, so only rows t < 2^(L - Ee),
@@ -818,21 +884,13 @@ __global__ __launch_bounds__(NTT_THREADS, 5) void k_dom_pass(uint8_t* __restrict
                                                                          int logC, uint32_t ntiles, DomArgs A) {
     __shared__ uint4 lds[NTT_TILE * 2];
     const uint32_t C = 1u << logC;
-    const uint32_t rows = 1u << L;
-    const uint32_t T = rows * C;
-    const uint32_t tiles_per_poly = (uint32_t)(((size_t)1 << log_n) >> (L + logC));
-    const uint4* twa = reinterpret_cast<const uint4*>(tw_);
-    const uint4* twb = twa + tw_count;
-    const uint32_t* twc = reinterpret_cast<const uint32_t*>(twa + 2 * (size_t)tw_count);
+    const uint32_t T = C << L;
     const uint32_t colbits = (uint32_t)(log_n - L);
-    const uint32_t lo_tiles = FIRST ? 1u : (1u << s0) >> logC;
     const uint32_t id = blockIdx.x;  // one tile per workgroup
     if (id >= ntiles) return;
-    const uint32_t poly = id / tiles_per_poly, tile = id % tiles_per_poly;
-    const uint32_t lo0 = FIRST ? tile * C : (tile % lo_tiles) * C;
-    const uint32_t hi_base = FIRST ? 0u : (tile / lo_tiles) << (s0 + L);
-    const uint4* in = reinterpret_cast<const uint4*>(in_) + 2 * (size_t)poly * A.in_stride;
-    uint4* o = reinterpret_cast<uint4*>(out_) + 2 * (size_t)poly * A.out_stride;
+    const Tile g = tile_of<FIRST>(id, log_n, s0, L, logC);
+    const uint4* in = reinterpret_cast<const uint4*>(in_) + 2 * (size_t)g.poly * A.in_stride;
+    uint4* o = reinterpret_cast<uint4*>(out_) + 2 * (size_t)g.poly * A.out_stride;
     const uint32_t smask = (1u << A.sh) - 1;
     const int Ee = (FIRST && !INV) ? A.E : 0;
 
@@ -842,7 +900,7 @@ __global__ __launch_bounds__(NTT_THREADS, 5) void k_dom_pass(uint8_t* __restrict
 #pragma clang loop vectorize(disable) interleave(disable)
         for (uint32_t e = threadIdx.x; e < Tl; e += NTT_THREADS) {
             const uint32_t c = e & (C - 1), t = e >> logC;
-            const uint32_t idx = (t << colbits) + lo0 + c;
+            const uint32_t idx = (t << colbits) + g.lo0 + c;
             Fr v;
             if (INV) {
                 v = ld2(in, idx);
@@ -860,12 +918,12 @@ __global__ __launch_bounds__(NTT_THREADS, 5) void k_dom_pass(uint8_t* __restrict
     } else {
 #pragma clang loop vectorize(disable) interleave(disable)
         for (uint32_t e = threadIdx.x; e < T; e += NTT_THREADS)
-            st2(lds, e, ld2(in, hi_base + ((e >> logC) << s0) + lo0 + (e & (C - 1))));
+            st2(lds, e, ld2(in, g.hi_base + ((e >> logC) << s0) + g.lo0 + (e & (C - 1))));
     }
     __syncthreads();
-    const uint32_t lo_base = FIRST ? 0u : lo0;
-    // the last store of a value at position dst of its member
-    auto fin_store = [&](uint32_t dst, Fr v) {
+    // the last store of a finished value, at position dst of its member
+    auto put = [&](uint32_t row, uint32_t c, Fr v) {
+        const uint32_t dst = tile_dst<FIRST>(g, row, c, log_n, s0, L);
         if (INV && LAST) {
             // v < 2r: the first product is by a canonical factor and reduces
             if (A.tabA) v = (v * ld2(A.tabA, dst >> A.sh)) * ld2(A.tabB, dst & smask);
@@ -876,89 +934,8 @@ __global__ __launch_bounds__(NTT_THREADS, 5) void k_dom_pass(uint8_t* __restrict
             st2(o, dst, v);
         }
     };
-    auto put = [&](uint32_t row, uint32_t c, const Fr& v) {
-        fin_store(FIRST ? (bitrev(lo0 + c, colbits) << L) + row : hi_base + (row << s0) + lo0 + c, v);
-    };
-    // one stage pair; TRIV: the first pair of an unpruned first pass (j = 0, twiddles 1)
-    auto pair = [&](int l, auto triv_c) {
-        constexpr bool triv = decltype(triv_c)::value;
-        const bool fin = l + 2 > L;
-        const uint32_t h = 1u << (l - 1);
-        const int s = s0 + l;
-        const uint32_t t1 = (1u << (s - 1)) - 1, t2 = (1u << s) - 1;
-        const uint32_t stride = h * C;
-        for (uint32_t u = threadIdx.x; u < T / 4; u += NTT_THREADS) {
-            const uint32_t c = u & (C - 1);
-            const uint32_t r = u >> logC;
-            const uint32_t j = r & (h - 1);
-            const uint32_t q = ((r >> (l - 1)) << (l + 1)) + j;
-            const uint32_t e0 = q * C + c;
-            const uint32_t lo = FIRST ? 0u : lo_base + c;
-            r29::F29 w1, w2, w3;
-            const uint32_t jl = (j << s0) + lo;
-            if (!triv) {
-                w1 = ldtw(twa, twb, twc, t1 + jl);
-                w2 = ldtw(twa, twb, twc, t2 + jl);
-            }
-            w3 = ldtw(twa, twb, twc, t2 + jl + (h << s0));
-            Fr x0 = ld2(lds, e0), x1 = ld2(lds, e0 + stride), x2 = ld2(lds, e0 + 2 * stride),
-               x3 = ld2(lds, e0 + 3 * stride);
-            if (!triv) {
-                x1 = r29::mul_words(x1, w1);
-                x3 = r29::mul_words(x3, w1);
-            }
-            Fr y0 = add_2r(x0, x1), y1 = sub_2r(x0, x1), y2 = add_2r(x2, x3), y3 = sub_2r(x2, x3);
-            if (!triv) y2 = r29::mul_words(y2, w2);
-            y3 = r29::mul_words(y3, w3);
-            if (fin) {
-                put(q, c, add_2r(y0, y2));
-                put(q + 2 * h, c, sub_2r(y0, y2));
-                put(q + h, c, add_2r(y1, y3));
-                put(q + 3 * h, c, sub_2r(y1, y3));
-            } else {
-                st2(lds, e0, add_2r(y0, y2));
-                st2(lds, e0 + 2 * stride, sub_2r(y0, y2));
-                st2(lds, e0 + stride, add_2r(y1, y3));
-                st2(lds, e0 + 3 * stride, sub_2r(y1, y3));
-            }
-        }
-    };
-    int l = Ee + 1;
-    for (; l + 1 <= L; l += 2) {
-        if (FIRST && l == 1) pair(l, std::true_type{});
-        else pair(l, std::false_type{});
-        if (l + 2 > L) return;
-        __syncthreads();
-    }
-    if (l == L) {  // one radix-2 stage left
-        const uint32_t half = 1u << (l - 1);
-        const int s = s0 + l;
-        const uint32_t ts = (1u << (s - 1)) - 1;
-        for (uint32_t u = threadIdx.x; u < T / 2; u += NTT_THREADS) {
-            const uint32_t c = u & (C - 1);
-            const uint32_t r = u >> logC;
-            const uint32_t gg = r >> (l - 1);
-            const uint32_t j = r & (half - 1);
-            const uint32_t t0 = (gg << l) + j, t1 = t0 + half;
-            r29::F29 w;
-            if (l > 1 || !FIRST) w = ldtw(twa, twb, twc, ts + (j << s0) + (FIRST ? 0u : lo_base + c));
-            const Fr a = ld2(lds, t0 * C + c);
-            Fr b = ld2(lds, t1 * C + c);
-            if (l > 1 || !FIRST) b = r29::mul_words(b, w);
-            put(t0, c, add_2r(a, b));
-            put(t1, c, sub_2r(a, b));
-        }
-        return;
-    }
-    // ---- no stage left (L == 0, or every stage of the pass was replication): store the tile
-    for (uint32_t e = threadIdx.x; e < T; e += NTT_THREADS) {
-        if (FIRST) {
-            const uint32_t p = e & (rows - 1), c = e >> L;
-            put(p, c, ld2(lds, p * C + c));
-        } else {
-            put(e >> logC, e & (C - 1), ld2(lds, e));
-        }
-    }
+    // the replicated stages 1..Ee are done: the butterflies start at Ee + 1
+    tile_stages<FIRST, TrivPair::peeled>(lds, tw_, tw_count, Ee + 1, s0, L, logC, g.lo0, put);
 }
 
 // size-1 transforms: out = in (* vanishing_inv[0]); g^0 = N^-1 = 1
@@ -974,36 +951,12 @@ __global__ void k_dom_point(uint8_t* out, const uint8_t* in, const uint8_t* vinv
 __global__ void k_dom_tables(uint8_t* A, uint32_t nA, uint8_t* B, uint32_t nB, Fr g, int sh, Fr scale) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nA + nB) return;
-    uint64_t e = i < nA ? (uint64_t)i << sh : (uint64_t)(i - nA);
-    Fr acc = Fr::one(), b = g;
-    while (e) {
-        if (e & 1) acc = acc * b;
-        b = sqr(b);
-        e >>= 1;
-    }
+    const Fr acc = fr_pow(g, i < nA ? (uint64_t)i << sh : (uint64_t)(i - nA));
     if (i < nA) store<FrCfg>(A + 32 * (size_t)i, acc * scale);
     else store<FrCfg>(B + 32 * (size_t)(i - nA), acc);
 }
 
 static constexpr size_t MAX_COSETS = 8;
-static constexpr int DOM_MAX_LOG = 30;   // as ntt_call: sizes are ints, indices 32-bit
-static constexpr int DOM_MAX_PASSES = 4; // ceil(30 / 8)
-
-// ntt_device's pass plan: (s0, L, logC) per pass; returns the pass count (0 for log_n == 0)
-static int dom_passes(int log_n, int (*pl)[3]) {
-    const int npass = (log_n + NTT_PASS_STAGES - 1) / NTT_PASS_STAGES;
-    int s0 = 0;
-    for (int p = 0; p < npass; ++p) {
-        const int remaining = log_n - s0;
-        const int L = (remaining + (npass - p) - 1) / (npass - p);
-        const int colspace = p == 0 ? (log_n - L) : s0;
-        int logC = NTT_TILE_LOG - L;
-        if (logC > colspace) logC = colspace;
-        pl[p][0] = s0, pl[p][1] = L, pl[p][2] = logC;
-        s0 += L;
-    }
-    return npass;
-}
 
 static int ceil_log2(long long n) {
     int k = 0;
@@ -1014,9 +967,9 @@ static int ceil_log2(long long n) {
 static eIcicleError domain_plan(int size, int extended_size, int32_t* out) {
     if (!out) return MBLS_INVALID_POINTER;
     const int K = log2_exact(extended_size);
-    if (K < 0 || K > DOM_MAX_LOG || size < 1 || size > extended_size) return MBLS_INVALID_ARGUMENT;
-    int pl[DOM_MAX_PASSES][3];
-    const int np = dom_passes(K, pl);
+    if (K < 0 || K > NTT_MAX_LOG || size < 1 || size > extended_size) return MBLS_INVALID_ARGUMENT;
+    int pl[NTT_MAX_PASSES][3];
+    const int np = pass_plan(K, 1, pl);
     const int E = K - ceil_log2(size);
     const int L0 = np ? pl[0][1] : 0;
     const int Ee = E < L0 ? E : L0;
@@ -1032,10 +985,13 @@ static eIcicleError domain_plan(int size, int extended_size, int32_t* out) {
 }
 
 // the coset tables of (g, log_n, sh, inverse) on the current device, built on `st` (and waited
-// for, once) when the cache lacks them; caller holds g_domain_mu.  `evicted` takes a table pushed
-// out of the cache: the caller drops it after releasing the lock (its destructor synchronises).
-static eIcicleError coset_tables(Domain& dom, const uint64_t* g, int log_n, int sh, bool inverse, hipStream_t st,
-                                 std::shared_ptr<CosetTables>& got, std::shared_ptr<CosetTables>& evicted) {
+// for, once) when the cache lacks them; caller holds g_domain_mu (domain_snapshot).  w.evicted takes a
+// table pushed out of the cache: the caller lets it go outside the lock (its destructor synchronises).
+static eIcicleError coset_tables(Domain& dom, int log_n, hipStream_t st, CosetWant& w) {
+    const uint64_t* g = w.g;
+    const int sh = w.sh;
+    const bool inverse = w.inverse;
+    std::shared_ptr<CosetTables>&got = w.got, &evicted = w.evicted;
     for (size_t k = 0; k < dom.cosets.size(); ++k) {
         const CosetTables& c = *dom.cosets[k];
         if (c.log_n == log_n && c.sh == sh && c.inverse == inverse && hfr_eq(c.g, g)) {
@@ -1058,9 +1014,7 @@ static eIcicleError coset_tables(Domain& dom, const uint64_t* g, int log_n, int 
     memcpy(scale, HFR_ONE, 32);
     if (inverse) {
         hfr_inv(base, g);
-        uint64_t nm[4] = {(uint64_t)1 << log_n, 0, 0, 0};
-        hfr_mul(nm, nm, HFR_R2);
-        hfr_inv(scale, nm);
+        hfr_ninv(scale, log_n);
     }
     hipLaunchKernelGGL(k_dom_tables, dim3((nA + nB + 255) / 256), dim3(256), 0, st, t->mem, nA, t->mem + 32 * (size_t)nA,
                        nB, to_dev(base), sh, to_dev(scale));
@@ -1083,50 +1037,28 @@ static eIcicleError domain_call(bool inverse, const mbls_fr_t* input, int in_cou
                                 const NTTConfig* cfg, mbls_fr_t* output) {
     if (!input || !output || !cfg) return MBLS_INVALID_POINTER;
     const int K = log2_exact(extended_size);
-    if (K < 0 || K > DOM_MAX_LOG) return MBLS_INVALID_ARGUMENT;
+    if (K < 0 || K > NTT_MAX_LOG) return MBLS_INVALID_ARGUMENT;
     const int part = inverse ? out_count : in_count;  // size or out_size
     if (part < 1 || part > extended_size) return MBLS_INVALID_ARGUMENT;
     if (cfg->columns_batch || (int)cfg->ordering != MBLS_ORDERING_NN) return MBLS_INVALID_ARGUMENT;
     if (inverse && vanishing_inv && (log2_exact(period) < 0 || period > extended_size)) return MBLS_INVALID_ARGUMENT;
-    bool coset = false;
     uint64_t g[4];
-    if (coset_gen) {
-        memcpy(g, coset_gen->limbs, 32);
-        uint64_t gr[4];
-        hfr_mul(gr, g, HFR_R2);  // g R mod r, canonical for any 256-bit g
-        const uint64_t zero[4] = {0, 0, 0, 0};
-        if (hfr_eq(gr, zero)) return MBLS_INVALID_ARGUMENT;
-        coset = !hfr_eq(g, HFR_ONE);
-    }
+    const int kind = coset_kind(coset_gen, g);
+    if (kind < 0) return MBLS_INVALID_ARGUMENT;
     const int batch = cfg->batch_size > 0 ? cfg->batch_size : 1;
     const size_t N = (size_t)1 << K;
-    int pl[DOM_MAX_PASSES][3];
-    const int np = dom_passes(K, pl);
-    for (int p = 0; p < np; ++p)
-        if ((N >> (pl[p][1] + pl[p][2])) * (size_t)batch > 0x7fffffff) return MBLS_INVALID_ARGUMENT;
+    int pl[NTT_MAX_PASSES][3];
+    const int np = pass_plan(K, batch, pl);
+    if (np < 0) return MBLS_INVALID_ARGUMENT;
     hipStream_t st = static_cast<hipStream_t>(cfg->stream);
     // forward: i = (t << colbits) + c of the first pass; inverse: i = (row << s0) + lo of the last
     const int sh = np ? (inverse ? pl[np - 1][0] : K - pl[0][1]) : 0;
 
     std::shared_ptr<DomainTables> tables, superseded;
-    std::shared_ptr<CosetTables> ctab, evicted;
-    {
-        std::lock_guard<std::mutex> lk(g_domain_mu);
-        Domain* dom = current_domain();
-        if (!dom) return MBLS_INVALID_DEVICE;
-        if (K > dom->order_log) return MBLS_INVALID_ARGUMENT;  // beyond the initialised root
-        if (!dom->tables || dom->tables->max_log < K) {
-            int want = K < 20 ? 20 : K;
-            if (want > dom->order_log) want = dom->order_log;
-            eIcicleError er = build_domain(*dom, want, st, superseded);
-            if (er != MBLS_SUCCESS) return er;
-        }
-        tables = dom->tables;
-        if (coset && np) {
-            eIcicleError er = coset_tables(*dom, g, K, sh, inverse, st, ctab, evicted);
-            if (er != MBLS_SUCCESS) return er;
-        }
-    }
+    CosetWant cw{g, sh, inverse, nullptr, nullptr};
+    eIcicleError er = domain_snapshot(K, st, tables, superseded, kind > 0 && np ? &cw : nullptr);
+    if (er != MBLS_SUCCESS) return er;
+    const std::shared_ptr<CosetTables>& ctab = cw.got;
     const bool in_dev = cfg->are_inputs_on_device, out_dev = cfg->are_outputs_on_device;
     const size_t in_stride = inverse ? N : (size_t)in_count, out_stride = inverse ? (size_t)out_count : N;
     Staging S(st, Staging::LEASE_IF_STAGED);
@@ -1136,8 +1068,7 @@ static eIcicleError domain_call(bool inverse, const mbls_fr_t* input, int in_cou
     if (inverse && vanishing_inv) S.in(&vdev, vanishing_inv, (size_t)period * 32, in_dev);
     S.out(&dst, output, out_stride * 32 * batch, out_dev);
     if (inverse && np > 1) S.scratch(&work, N * 32 * batch);  // the input is const, the output too short
-    eIcicleError er = S.open();
-    if (er != MBLS_SUCCESS) return er;
+    if ((er = S.open()) != MBLS_SUCCESS) return er;
 
     if (np == 0) {
         hipLaunchKernelGGL(k_dom_point, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, dst, src, vdev,
@@ -1155,37 +1086,28 @@ static eIcicleError domain_call(bool inverse, const mbls_fr_t* input, int in_cou
     A.vinv = reinterpret_cast<const uint4*>(vdev), A.vmask = vdev ? (uint32_t)period - 1 : 0;
     uint64_t ninv_h[4];
     memcpy(ninv_h, HFR_ONE, 32);
-    if (inverse) {
-        uint64_t nm[4] = {N, 0, 0, 0};
-        hfr_mul(nm, nm, HFR_R2);
-        hfr_inv(ninv_h, nm);
-    }
+    if (inverse) hfr_ninv(ninv_h, K);
     A.scale = to_dev(ninv_h);
     const uint8_t* tw = inverse ? tables->tw_inv : tables->tw;
-    const uint32_t twn = tables->count;
     uint8_t* wbuf = inverse ? work : dst;  // where the passes between the first and the last work
     ProfScope prof_t(inverse ? "domain.extended_to_coeff" : "domain.coeff_to_extended", st);
     for (int p = 0; p < np; ++p) {
-        const int s0 = pl[p][0], L = pl[p][1], logC = pl[p][2];
         const bool first = p == 0, last = p == np - 1;
-        const uint32_t nt = (uint32_t)((N >> (L + logC)) * (size_t)batch);
-        dim3 grid(nt), blk(NTT_THREADS);
-        DomArgs a = A;
-        if (first && last) {
-            if (inverse) hipLaunchKernelGGL((k_dom_pass<true, true, true>), grid, blk, 0, st, dst, src, tw, twn, K, s0, L, logC, nt, a);
-            else hipLaunchKernelGGL((k_dom_pass<true, true, false>), grid, blk, 0, st, dst, src, tw, twn, K, s0, L, logC, nt, a);
-        } else if (first) {
-            a.out_stride = (uint32_t)N;
-            if (inverse) hipLaunchKernelGGL((k_dom_pass<true, false, true>), grid, blk, 0, st, wbuf, src, tw, twn, K, s0, L, logC, nt, a);
-            else hipLaunchKernelGGL((k_dom_pass<true, false, false>), grid, blk, 0, st, wbuf, src, tw, twn, K, s0, L, logC, nt, a);
-        } else if (last && inverse) {
-            a.in_stride = (uint32_t)N;
-            hipLaunchKernelGGL((k_dom_pass<false, true, true>), grid, blk, 0, st, dst, wbuf, tw, twn, K, s0, L, logC, nt, a);
-        } else if (last) {
-            hipLaunchKernelGGL((k_ntt_pass<false, true, false>), grid, blk, 0, st, wbuf, wbuf, tw, twn, K, s0, L, logC, A.scale, nt);
-        } else {
-            hipLaunchKernelGGL((k_ntt_pass<false, false, false>), grid, blk, 0, st, wbuf, wbuf, tw, twn, K, s0, L, logC, A.scale, nt);
+        if (!first && !(last && inverse)) {  // the plain transform's pass as it stands
+            er = launch_ntt_pass(false, last, inverse, wbuf, wbuf, tw, tables->count, K, pl[p], A.scale, batch, st);
+            if (er != MBLS_SUCCESS) return er;
+            continue;
         }
+        const int s0 = pl[p][0], L = pl[p][1], logC = pl[p][2];
+        const uint32_t nt = (uint32_t)pass_tiles(K, L, logC, batch);
+        DomArgs a = A;
+        if (!first) a.in_stride = (uint32_t)N;
+        if (!last) a.out_stride = (uint32_t)N;
+        auto* k = k_dom_pass<false, true, true>;
+        if (first && last) k = inverse ? k_dom_pass<true, true, true> : k_dom_pass<true, true, false>;
+        else if (first) k = inverse ? k_dom_pass<true, false, true> : k_dom_pass<true, false, false>;
+        hipLaunchKernelGGL(k, dim3(nt), dim3(NTT_THREADS), 0, st, last ? dst : wbuf, first ? src : wbuf, tw, tables->count,
+                           K, s0, L, logC, nt, a);
         MBLS_TRY(hipGetLastError());
     }
     return S.close(cfg->is_async);

@@ -63,7 +63,7 @@ def kernel_defaults():
 
 
 def plan(log_n, tile_log=None, pass_stages=None):
-    """ntt_device's pass plan: [(s0, L, logC)] for a transform of 2^log_n (log_n >= 1)"""
+    """ntt.hip's pass plan (pass_plan): [(s0, L, logC)] for a transform of 2^log_n (log_n >= 1)"""
     if tile_log is None or pass_stages is None:
         tile_log, pass_stages = kernel_defaults()
     npass = (log_n + pass_stages - 1) // pass_stages

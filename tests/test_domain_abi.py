@@ -46,6 +46,8 @@ def _sizes(N):
 
 
 def test_plan_equals_the_model(built):
+    """mbls_fr_domain_plan reports ntt.hip's one pass plan (pass_plan), which the plain NTT
+    (ntt_device) runs as well as the domain transforms: this pins the plan of both to ntt_model.plan."""
     amd = A._amd()
     for K in range(13):
         for size in _sizes(1 << K):

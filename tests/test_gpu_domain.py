@@ -309,6 +309,24 @@ def test_scratch_use(amd, plain_before):
     assert amd.domain_plan(size, N)["fwd_scratch"] == 0 and amd.domain_plan(size, N)["inv_scratch"] == N
 
 
+# ----------------------------------------------------------------------------- one engine, two kernels
+@gpu
+@pytest.mark.parametrize("K", [1, 2, 3, 8, 9, 12, 13, 17])
+def test_full_size_unit_coset_equals_plain_ntt(amd, plain_before, K):
+    """k_dom_pass and k_ntt_pass run one stage engine in different modes, so with nothing for the
+    domain passes to add (size = N: no pruning; no generator; no vanishing table; out_size = N) they
+    give the plain transforms' bytes.  The sizes are the plan shapes of test_gpu_ntt.py's
+    test_pass_plans_of_the_gpu_sizes: the lone radix-2 stage, the trivial pair alone, pair + tail, the
+    largest single pass, clamped logC, full tiles, an odd L in a first pass that is not the last (13,
+    which no other test of this module runs), and the first plan with a middle pass."""
+    N = 1 << K
+    # canonical, seeded; the seeds are those of test_forward_2_17 and test_forward_vs_model, so that
+    # _rand_limbs' cache hands back their arrays and 2^17 values are not drawn and converted twice
+    _, x = _rand_limbs(0x17 if K == 17 else 0xF0 + K, N)
+    assert np.array_equal(amd.coeff_to_extended(x.copy(), N, None), amd.ntt(x.copy())), K
+    assert np.array_equal(amd.extended_to_coeff(x.copy(), N, None, None), amd.ntt(x.copy(), inverse=True)), K
+
+
 # ----------------------------------------------------------------------------- the NTT entries, after
 @gpu
 def test_plain_ntt_unchanged_afterwards(amd, plain_before):
