@@ -491,6 +491,57 @@ eIcicleError mbls_fr_expr_check(const mbls_fr_expr_op* program, int n_ops, int n
                                 int n_outputs, int32_t* out);
 
 /* ------------------------------------------------------------------------------------ */
+/* Fr graph evaluator: the same work as mbls_fr_eval_program for a program in three-address form
+ * over named values -- the form of halo2's GraphEvaluator, whose calculations each write one
+ * intermediate that any later calculation may read.  Op k defines value k (single assignment), so a
+ * subexpression shared by several constraints is computed once.  One launch.  (No reference
+ * counterpart.)
+ *   as mbls_fr_eval_program: the element form (Montgomery, canonical, in and out), the rotation
+ *     arithmetic (a COLUMN source reads row (i + rot * rot_stride) mod size, any rot, rot_stride in
+ *     1..2^26), size in 1..2^26, the placement flags (columns by is_a_on_device, constants by
+ *     is_b_on_device, output by is_result_on_device), the staging of host buffers, is_async, the
+ *     output layout (n_outputs members of size elements), and that output may overlap no column
+ *     (nor the constants, which the kernel reads through the scalar cache).
+ *   sources: `a` is read by every op, `b` by ADD, SUB, MUL and HORNER only and must be NONE on the
+ *     others.  idx of a NONE source, rot of a source that is no COLUMN, and c of an op that is
+ *     neither HORNER nor EMIT are not read.
+ *   limits: n_ops in 1..16384, n_columns in 1..1024, n_constants in 0..1024, n_outputs in 1..8,
+ *     at most 32 values resident at once (below).
+ *   residency: let last(j) be the largest op index that reads value j.  A read of value j by op
+ *     j + 1 is forwarded from the register that still holds it.  Value j is resident iff
+ *     last(j) > j + 1, and then occupies one slot of on-chip memory while ops j + 1 .. last(j) run.
+ *     The peak is the largest number of values resident during any one op; the budget is 32.  A
+ *     value nobody reads is allowed and costs nothing.  There is no spilling: a caller whose peak
+ *     is too high cuts the program at the op mbls_fr_graph_check names, emits the live values as
+ *     outputs and reads them back as columns in a second call.
+ *   errors, all before any device work: INVALID_POINTER as mbls_fr_eval_program; INVALID_ARGUMENT
+ *     for a size or count outside its limit, an unknown opcode or source kind, a b other than NONE
+ *     on SQUARE, DOUBLE, NEG, STORE or EMIT, NONE where an operand is needed, a VALUE index that is
+ *     negative, not smaller than the op's own, or names an EMIT, a column, constant or output index
+ *     out of range, an output emitted twice or never, a peak above the budget.
+ *   timing: no branch and no address depends on a field value.                                   */
+/* ------------------------------------------------------------------------------------ */
+typedef enum { MBLS_GRAPH_ADD = 0, MBLS_GRAPH_SUB, MBLS_GRAPH_MUL, MBLS_GRAPH_SQUARE, MBLS_GRAPH_DOUBLE,
+               MBLS_GRAPH_NEG, MBLS_GRAPH_HORNER /* a * constants[c] + b */, MBLS_GRAPH_STORE /* a */,
+               MBLS_GRAPH_EMIT /* output[c * size + i] = a, defines no value */ } mbls_fr_graph_opcode;
+typedef enum { MBLS_GRAPH_NONE = 0, MBLS_GRAPH_VALUE /* result of op idx, idx < this op */,
+               MBLS_GRAPH_COLUMN /* columns[idx][(i + rot * rot_stride) mod size] */,
+               MBLS_GRAPH_CONST  /* constants[idx] */ } mbls_fr_graph_source;
+typedef struct { int32_t kind, idx, rot; } mbls_fr_graph_src;
+typedef struct { int32_t op; mbls_fr_graph_src a, b; int32_t c; } mbls_fr_graph_op;   /* 32 bytes */
+
+eIcicleError mbls_fr_eval_graph(const mbls_fr_t* const* columns, int n_columns, size_t size, size_t rot_stride,
+                                const mbls_fr_t* constants, int n_constants, const mbls_fr_graph_op* program,
+                                int n_ops, int n_outputs, const VecOpsConfig* config, mbls_fr_t* output);
+/* host only, no device work: the same validation, and a description of the program.
+ * out[0] = peak, out[1] = the first op index at which the peak is reached, out[2] = resident values,
+ * out[3] = forwarded operands, out[4] = column loads per row, out[5] = distinct (column, rot) pairs,
+ * out[6] = products per row (MUL, SQUARE, HORNER), out[7] = the budget.  A program refused only for
+ * its peak still gets all eight written, so that the caller knows where to cut. */
+eIcicleError mbls_fr_graph_check(const mbls_fr_graph_op* program, int n_ops, int n_columns, int n_constants,
+                                 int n_outputs, int32_t* out);
+
+/* ------------------------------------------------------------------------------------ */
 /* batch point-form conversions, reference point_ops.cu:759 / :844 / :924 (exported there as
  * extern "C").  Montgomery in, Montgomery out; Jacobian projective (x = X/Z^2, y = Y/Z^3).
  * affine_to_projective: (x, y) -> (x, y, 1), identity (0, 0) -> (0, 1, 0).

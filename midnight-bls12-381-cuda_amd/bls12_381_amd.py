@@ -83,7 +83,7 @@ EXPORTED = [
     "mbls_g1_check_points", "mbls_g2_check_points",
     "mbls_g1_decompress", "mbls_g2_decompress", "mbls_g1_compress", "mbls_g2_compress",
     "mbls_fr_prefix_product", "mbls_fr_poly_divide_linear", "mbls_fr_scan_geometry",
-    "mbls_fr_eval_program", "mbls_fr_expr_check",
+    "mbls_fr_eval_program", "mbls_fr_expr_check", "mbls_fr_eval_graph", "mbls_fr_graph_check",
     "mbls_fr_sort", "mbls_fr_lookup_permute", "mbls_fr_sort_plan",
     "mbls_fr_coeff_to_extended", "mbls_fr_extended_to_coeff", "mbls_fr_domain_plan",
     "mbls_fr_lookup_multiplicities", "mbls_fr_prefix_sum", "mbls_fr_logup_sum",
@@ -144,6 +144,8 @@ def lib():
         "mbls_fr_scan_geometry": [sz, P],
         "mbls_fr_eval_program": [P, i32, sz, sz, P, i32, P, i32, i32, P, P],
         "mbls_fr_expr_check": [P, i32, i32, i32, i32, P],
+        "mbls_fr_eval_graph": [P, i32, sz, sz, P, i32, P, i32, i32, P, P],
+        "mbls_fr_graph_check": [P, i32, i32, i32, i32, P],
         "mbls_fr_sort": [P, sz, b, P, P, P], "mbls_fr_lookup_permute": [P, P, sz, b, P, P, P, P],
         "mbls_fr_sort_plan": [sz, i32, P],
         "mbls_fr_coeff_to_extended": [P, i32, i32, P, P, P],
@@ -727,6 +729,64 @@ def eval_program(columns, program, *, constants=None, n_outputs=1, rot_stride=1,
     check(lib().mbls_fr_eval_program(table, len(columns), n, rot_stride, _p(constants),
                                      0 if constants is None else constants.shape[0], _expr_program(program), len(program),
                                      n_outputs, ctypes.byref(cfg), _p(out)), "mbls_fr_eval_program")
+    return out
+
+
+# ----------------------------------------------------------------------------- graph evaluator
+(GRAPH_ADD, GRAPH_SUB, GRAPH_MUL, GRAPH_SQUARE, GRAPH_DOUBLE, GRAPH_NEG, GRAPH_HORNER, GRAPH_STORE,
+ GRAPH_EMIT) = range(9)
+(GRAPH_NONE, GRAPH_VALUE, GRAPH_COLUMN, GRAPH_CONST) = range(4)
+GRAPH_CHECK_FIELDS = ("peak", "peak_at", "resident", "forwarded", "loads", "pairs", "muls", "budget")
+
+
+class GraphSrc(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("idx", ctypes.c_int32), ("rot", ctypes.c_int32)]
+
+
+class GraphOp(ctypes.Structure):
+    _fields_ = [("op", ctypes.c_int32), ("a", GraphSrc), ("b", GraphSrc), ("c", ctypes.c_int32)]
+
+
+def _graph_program(program):
+    """(op, a, b, c) tuples, a and b (kind, idx, rot) triples, as one contiguous GraphOp array"""
+    flat = np.array([(op, *a, *b, c) for op, a, b, c in program], dtype=np.int32).reshape(-1, 8)
+    ops = (GraphOp * max(len(program), 1))()
+    ctypes.memmove(ops, flat.ctypes.data, flat.nbytes)
+    return ops
+
+
+def graph_check(program, n_columns, n_constants, n_outputs):
+    """validate and describe a graph program (mbls_fr_graph_check; host only): dict of
+    GRAPH_CHECK_FIELDS -- the peak of resident values, the first op at which it is reached, resident
+    values, forwarded operands, column loads and products per row, distinct (column, rot) pairs, the
+    budget.  Raises IcicleError(INVALID_ARGUMENT) for a malformed one; when only the peak is at fault
+    the error carries the same dict as `info`."""
+    out = (ctypes.c_int32 * len(GRAPH_CHECK_FIELDS))(*([-1] * len(GRAPH_CHECK_FIELDS)))
+    code = lib().mbls_fr_graph_check(_graph_program(program), len(program), n_columns, n_constants, n_outputs, out)
+    info = dict(zip(GRAPH_CHECK_FIELDS, list(out)))
+    if code != SUCCESS:
+        err = IcicleError(code, "mbls_fr_graph_check")
+        if out[0] >= 0:
+            err.info = info
+        raise err
+    return info
+
+
+def eval_graph(columns, program, *, constants=None, n_outputs=1, rot_stride=1, out=None, stream=None, is_async=False):
+    """Run `program`, a list of (op, a, b, c) tuples of GRAPH_* opcodes whose a and b are (kind, idx, rot)
+    sources, once per row (mbls_fr_eval_graph); op k defines value k.  columns, constants, out and the
+    result are as eval_program's."""
+    n = columns[0].shape[0]
+    on_dev = _is_dev(columns[0])
+    assert all(c.shape[0] == n and _is_dev(c) == on_dev for c in columns), "columns share one size and placement"
+    if out is None:
+        out = _like(columns[0], n_outputs * n)
+    table = (ctypes.c_void_p * len(columns))(*[_p(c) for c in columns])
+    cfg = vec_config(is_a_on_device=on_dev, is_b_on_device=_is_dev(constants), is_result_on_device=_is_dev(out),
+                     is_async=is_async, stream=stream)
+    check(lib().mbls_fr_eval_graph(table, len(columns), n, rot_stride, _p(constants),
+                                   0 if constants is None else constants.shape[0], _graph_program(program), len(program),
+                                   n_outputs, ctypes.byref(cfg), _p(out)), "mbls_fr_eval_graph")
     return out
 
 
