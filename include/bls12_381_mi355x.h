@@ -542,6 +542,74 @@ eIcicleError mbls_fr_graph_check(const mbls_fr_graph_op* program, int n_ops, int
                                  int n_outputs, int32_t* out);
 
 /* ------------------------------------------------------------------------------------ */
+/* Fr inner products and multi-point polynomial evaluation: the phase between the quotient and the
+ * multi-open of a halo2-style prover, where every committed polynomial is evaluated at the challenge
+ * x and its rotations omega^r x.  p(z) = sum_i a_i z^i is an inner product with the powers of z, and
+ * the powers are shared by every polynomial opened at z.  (No reference counterpart: the reference
+ * evaluates on the CPU, eval_polynomial, one Horner pass per polynomial and point.)
+ *   elements: Montgomery and canonical (< r), in and out; points, base and init likewise.  Every
+ *     output is canonical; a field sum is unique, so the result does not depend on the order of
+ *     summation.  init == NULL means Montgomery one.  z^0 = 1 for every z, 0 included.
+ *   pointer tables: `columns` and `vectors` are host arrays of pointers, always, as `columns` is for
+ *     mbls_fr_eval_program; what they point to is placed by the config.
+ *   placement: config->is_a_on_device the columns (all alike), is_b_on_device the vectors (all
+ *     alike), points, base and init, is_result_on_device the output.  Host operands are staged
+ *     through the leased scratch context, which also holds every work array (no allocation per call
+ *     once it is large enough; mbls_fr_inner_plan reports the bytes); a host output makes the call
+ *     synchronous, otherwise it synchronises unless is_async.
+ *   batch: mbls_fr_inner_products and mbls_fr_multi_eval do not read batch_size or columns_batch.
+ *     mbls_fr_powers reads batch_size (0 counts as 1): member k fills rows k * size .. (k + 1) * size
+ *     from base[k] and init[k]; columns_batch gives API_NOT_IMPLEMENTED, as the scans do.
+ *   limits: size in 1..2^26 (mbls_fr_powers: size * batch <= 2^26), n_columns in 1..1024,
+ *     n_vectors and n_points in 1..16.
+ *   errors, all before any device work: INVALID_POINTER for a null table, points, base, config or
+ *     output and for a null table entry; INVALID_ARGUMENT for a size or count outside its limit.
+ *   overlap: the output must not overlap any input; otherwise the result is undefined.
+ *   timing: the columns are witness polynomials: no branch and no address depends on a field value.
+ *     The conditions are on thread, block and row indices and on the counts; the power tables are
+ *     built by square-and-multiply over the bits of a row index, never of a base.
+ *   work: a workgroup takes CB columns x VB vectors and loads each element of a row once for the
+ *     CB * VB products; the products are radix 2^29 and a thread adds the unreduced columns of 7 of
+ *     them into 64-bit accumulators before one Montgomery reduction (7 * 9 * 2^58 < 2^64).  Each
+ *     workgroup writes one partial sum per output of its block and a second launch folds them;
+ *     their number is bounded by the plan, not by `size`.  mbls_fr_multi_eval writes the powers of
+ *     each point to scratch (mbls_fr_powers' kernels, 32 * size * n_points bytes) and runs the same
+ *     inner products over them, so it equals mbls_fr_powers followed by mbls_fr_inner_products.
+ *     mbls_fr_powers costs one product per element: base^i = hi[i >> s] * lo[i & (2^s - 1)] with two
+ *     tables of about sqrt(size) entries per member, hi carrying init.
+ *   which call: for ONE polynomial at ONE point mbls_fr_poly_divide_linear with quotient == NULL
+ *     does not write the powers and may be as fast; mbls_fr_multi_eval is for several polynomials
+ *     sharing their points.                                                       */
+/* ------------------------------------------------------------------------------------ */
+/* output[p * n_vectors + k] = sum_{i < size} columns[p][i] * vectors[k][i] */
+eIcicleError mbls_fr_inner_products(const mbls_fr_t* const* columns, int n_columns,
+                                    const mbls_fr_t* const* vectors, int n_vectors, size_t size,
+                                    const VecOpsConfig* config, mbls_fr_t* output);
+/* output[p * n_points + k] = sum_{i < size} columns[p][i] * points[k]^i   (z^0 = 1, also for z = 0) */
+eIcicleError mbls_fr_multi_eval(const mbls_fr_t* const* columns, int n_columns, size_t size,
+                                const mbls_fr_t* points, int n_points,
+                                const VecOpsConfig* config, mbls_fr_t* output);
+/* output[k * size + i] = init[k] * base[k]^i, k < batch;  init == NULL means Montgomery one */
+eIcicleError mbls_fr_powers(const mbls_fr_t* base, const mbls_fr_t* init, size_t size,
+                            const VecOpsConfig* config, mbls_fr_t* output);
+/* host only, no device work: the geometry the three calls use for `size` rows, n_columns columns and
+ * n_vectors vectors (or points).  Twelve words:
+ *   out[0] = T, rows per tile (threads * out[1]),
+ *   out[1] = products a thread defers before one reduction = rows it takes from a tile,
+ *   out[2] = CB, columns per block,  out[3] = VB, vectors per block,
+ *   out[4] = the maximum number of workgroups of the product launch, whatever the size,
+ *   out[5] = the most row groups these counts may take; a workgroup takes more than one tile only
+ *            for size > out[5] * T,
+ *   out[6] = consecutive tiles per workgroup,  out[7] = G, row groups = partial sums per output,
+ *   out[8] = workgroups launched = G * ceil(n_columns / CB) * ceil(n_vectors / VB),
+ *   out[9] = scratch bytes of mbls_fr_inner_products (staging not counted):
+ *            up256(32 * G * n_columns * n_vectors) + up256(8 * (n_columns + n_vectors)),
+ *   out[10] = scratch bytes of mbls_fr_multi_eval with n_points = n_vectors (staging not counted):
+ *            out[9] + up256(32 * n_vectors * (2^s + ceil(size / 2^s))) + up256(32 * size * n_vectors),
+ *   out[11] = s of the power tables;  up256 rounds up to a multiple of 256. */
+eIcicleError mbls_fr_inner_plan(size_t size, int n_columns, int n_vectors, int64_t* out);
+
+/* ------------------------------------------------------------------------------------ */
 /* batch point-form conversions, reference point_ops.cu:759 / :844 / :924 (exported there as
  * extern "C").  Montgomery in, Montgomery out; Jacobian projective (x = X/Z^2, y = Y/Z^3).
  * affine_to_projective: (x, y) -> (x, y, 1), identity (0, 0) -> (0, 1, 0).

@@ -87,6 +87,7 @@ EXPORTED = [
     "mbls_fr_sort", "mbls_fr_lookup_permute", "mbls_fr_sort_plan",
     "mbls_fr_coeff_to_extended", "mbls_fr_extended_to_coeff", "mbls_fr_domain_plan",
     "mbls_fr_lookup_multiplicities", "mbls_fr_prefix_sum", "mbls_fr_logup_sum",
+    "mbls_fr_inner_products", "mbls_fr_multi_eval", "mbls_fr_powers", "mbls_fr_inner_plan",
 ]
 
 _LIB = None
@@ -152,6 +153,8 @@ def lib():
         "mbls_fr_extended_to_coeff": [P, i32, i32, P, P, i32, P, P], "mbls_fr_domain_plan": [i32, i32, P],
         "mbls_fr_lookup_multiplicities": [P, i32, P, sz, b, b, P, P, P],
         "mbls_fr_prefix_sum": [P, sz, P, b, P, P, P], "mbls_fr_logup_sum": [P, i32, P, P, sz, P, P, P, P, P],
+        "mbls_fr_inner_products": [P, i32, P, i32, sz, P, P], "mbls_fr_multi_eval": [P, i32, sz, P, i32, P, P],
+        "mbls_fr_powers": [P, P, sz, P, P], "mbls_fr_inner_plan": [sz, i32, i32, P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -683,6 +686,74 @@ def logup_sum(inputs, table, m, beta, init=None, out=None, total=False, *, batch
     check(lib().mbls_fr_logup_sum(cols, len(inputs), _p(table), _p(m), n, _p(beta), _p(init), ctypes.byref(cfg), _p(out),
                                   _p(total)), "mbls_fr_logup_sum")
     return out if total is None else (out, total)
+
+
+# ----------------------------------------------------------------------------- inner products
+INNER_PLAN_FIELDS = ("tile", "defer", "CB", "VB", "max_workgroups", "group_cap", "tiles_per_group", "groups",
+                     "workgroups", "inner_bytes", "multi_eval_bytes", "pow_log")
+
+
+def inner_plan(n, n_columns=1, n_vectors=1):
+    """the geometry and scratch of inner_products / multi_eval for n rows (mbls_fr_inner_plan; host
+    only): dict of INNER_PLAN_FIELDS -- rows per tile, products deferred per reduction, columns and
+    vectors per block, the most workgroups of any call, the most row groups of these counts (a
+    workgroup takes several tiles only above group_cap * tile rows), tiles per workgroup, row groups,
+    workgroups launched, scratch bytes of inner_products and of multi_eval, the power tables' split"""
+    out = (ctypes.c_int64 * len(INNER_PLAN_FIELDS))()
+    check(lib().mbls_fr_inner_plan(n, n_columns, n_vectors, out), "mbls_fr_inner_plan")
+    return dict(zip(INNER_PLAN_FIELDS, list(out)))
+
+
+def _pointer_table(cols):
+    n, on_dev = cols[0].shape[0], _is_dev(cols[0])
+    assert all(c.shape[0] == n and _is_dev(c) == on_dev for c in cols), "the operands of a table share one size and placement"
+    return (ctypes.c_void_p * len(cols))(*[_p(c) for c in cols]), n, on_dev
+
+
+def inner_products(columns, vectors, *, out=None, stream=None, is_async=False):
+    """out[p * len(vectors) + k] = sum_i columns[p][i] * vectors[k][i] (mbls_fr_inner_products).
+    columns: a list of 1..1024 (n, 4) uint64 Montgomery columns, all numpy (host) or all torch
+    (device); vectors: a list of 1..16 such, placed alike among themselves.  Returns out,
+    (len(columns) * len(vectors), 4): `out` when given, else placed as the columns are."""
+    ctab, n, c_dev = _pointer_table(columns)
+    vtab, nv, v_dev = _pointer_table(vectors)
+    assert n == nv, "columns and vectors share one size"
+    if out is None:
+        out = _like(columns[0], len(columns) * len(vectors))
+    cfg = vec_config(is_a_on_device=c_dev, is_b_on_device=v_dev, is_result_on_device=_is_dev(out), is_async=is_async,
+                     stream=stream)
+    check(lib().mbls_fr_inner_products(ctab, len(columns), vtab, len(vectors), n, ctypes.byref(cfg), _p(out)),
+          "mbls_fr_inner_products")
+    return out
+
+
+def multi_eval(columns, points, *, out=None, stream=None, is_async=False):
+    """out[p * k_points + k] = columns[p] as a polynomial, lowest degree first, at points[k]
+    (mbls_fr_multi_eval).  columns: a list of 1..1024 (n, 4) uint64 Montgomery columns, all numpy or all
+    torch; points (1..16, 4), numpy or torch.  Returns out, (len(columns) * k_points, 4): `out` when
+    given, else placed as the columns are."""
+    ctab, n, c_dev = _pointer_table(columns)
+    if out is None:
+        out = _like(columns[0], len(columns) * points.shape[0])
+    cfg = vec_config(is_a_on_device=c_dev, is_b_on_device=_is_dev(points), is_result_on_device=_is_dev(out),
+                     is_async=is_async, stream=stream)
+    check(lib().mbls_fr_multi_eval(ctab, len(columns), n, _p(points), points.shape[0], ctypes.byref(cfg), _p(out)),
+          "mbls_fr_multi_eval")
+    return out
+
+
+def powers(base, n, *, init=None, out=None, stream=None, is_async=False):
+    """out[k * n + i] = init[k] * base[k]^i (mbls_fr_powers), x^0 = 1 also for x = 0.  base (batch, 4)
+    uint64 Montgomery, init likewise and placed as base is, default Montgomery one.  Returns out,
+    (batch * n, 4): `out` when given, else placed as base is."""
+    batch = base.shape[0]
+    assert init is None or (init.shape[0] == batch and _is_dev(init) == _is_dev(base)), "base and init share shape and placement"
+    if out is None:
+        out = _like(base, batch * n)
+    cfg = vec_config(is_b_on_device=_is_dev(base), is_result_on_device=_is_dev(out), is_async=is_async, stream=stream,
+                     batch_size=batch)
+    check(lib().mbls_fr_powers(_p(base), _p(init), n, ctypes.byref(cfg), _p(out)), "mbls_fr_powers")
+    return out
 
 
 # ----------------------------------------------------------------------------- expression evaluator
