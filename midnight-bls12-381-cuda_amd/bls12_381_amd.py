@@ -615,10 +615,12 @@ def lookup_permute(input, table, *, mont=True, batch=1, count=True, out=None, st
 
 
 # ----------------------------------------------------------------------------- log-derivative lookup
-def _column_table(inputs, like):
+def _pointer_table(cols, like=None, what="the operands of a table share one size and placement"):
+    """(table, n, on_device) of a list of operands of one size and one placement, `like`'s when given"""
+    like = cols[0] if like is None else like
     n, on_dev = like.shape[0], _is_dev(like)
-    assert all(c.shape[0] == n and _is_dev(c) == on_dev for c in inputs), "columns and table share one size and placement"
-    return (ctypes.c_void_p * len(inputs))(*[_p(c) for c in inputs])
+    assert all(c.shape[0] == n and _is_dev(c) == on_dev for c in cols), what
+    return (ctypes.c_void_p * len(cols))(*[_p(c) for c in cols]), n, on_dev
 
 
 def lookup_multiplicities(inputs, table, credit="first", montgomery=True, *, batch=1, count=True, out=None, stream=None,
@@ -632,7 +634,7 @@ def lookup_multiplicities(inputs, table, credit="first", montgomery=True, *, bat
     for count=False (then a device output with is_async does not wait)."""
     assert credit in ("first", "last")
     n = table.shape[0] // batch
-    cols = _column_table(inputs, table)
+    cols, _, _ = _pointer_table(inputs, table, "columns and table share one size and placement")
     if out is None:
         out = _like(table, table.shape[0])
     cnt = (ctypes.c_uint64 * batch)() if count else None
@@ -671,7 +673,7 @@ def logup_sum(inputs, table, m, beta, init=None, out=None, total=False, *, batch
     array; with total=True, or a (batch, 4) buffer placed as `out`, returns (out, total), total =
     phi[n], zero for a satisfied lookup started from zero."""
     n = table.shape[0] // batch
-    cols = _column_table(inputs, table)
+    cols, _, _ = _pointer_table(inputs, table, "columns and table share one size and placement")
     assert m.shape[0] == table.shape[0] and _is_dev(m) == _is_dev(table), "m is sized and placed as the table is"
     assert init is None or _is_dev(init) == _is_dev(beta), "beta and init share one placement"
     if out is None:
@@ -702,12 +704,6 @@ def inner_plan(n, n_columns=1, n_vectors=1):
     out = (ctypes.c_int64 * len(INNER_PLAN_FIELDS))()
     check(lib().mbls_fr_inner_plan(n, n_columns, n_vectors, out), "mbls_fr_inner_plan")
     return dict(zip(INNER_PLAN_FIELDS, list(out)))
-
-
-def _pointer_table(cols):
-    n, on_dev = cols[0].shape[0], _is_dev(cols[0])
-    assert all(c.shape[0] == n and _is_dev(c) == on_dev for c in cols), "the operands of a table share one size and placement"
-    return (ctypes.c_void_p * len(cols))(*[_p(c) for c in cols]), n, on_dev
 
 
 def inner_products(columns, vectors, *, out=None, stream=None, is_async=False):
@@ -783,24 +779,26 @@ def expr_check(program, n_columns, n_constants, n_outputs):
     return dict(zip(EXPR_CHECK_FIELDS, list(out)))
 
 
+def _eval_rows(entry, name, ops, n_ops, columns, constants, n_outputs, rot_stride, out, stream, is_async):
+    """the body eval_program and eval_graph share: `entry` over `ops`, the program in its C form"""
+    table, n, on_dev = _pointer_table(columns, what="columns share one size and placement")
+    if out is None:
+        out = _like(columns[0], n_outputs * n)
+    cfg = vec_config(is_a_on_device=on_dev, is_b_on_device=_is_dev(constants), is_result_on_device=_is_dev(out),
+                     is_async=is_async, stream=stream)
+    check(entry(table, len(columns), n, rot_stride, _p(constants), 0 if constants is None else constants.shape[0], ops,
+                n_ops, n_outputs, ctypes.byref(cfg), _p(out)), name)
+    return out
+
+
 def eval_program(columns, program, *, constants=None, n_outputs=1, rot_stride=1, out=None, stream=None, is_async=False):
     """Run `program`, a list of (op, a, b) tuples of EXPR_* opcodes, once per row (mbls_fr_eval_program).
     columns: a list of (n, 4) uint64 Montgomery columns, all numpy (host) or all torch (device);
     COLUMN a, b reads columns[a][(i + b * rot_stride) mod n].  constants (k, 4), numpy or torch.
     Returns out, (n_outputs * n, 4) with output k at rows k * n .. (k + 1) * n: `out` when given (it may
     overlap no column), else placed as the columns are."""
-    n = columns[0].shape[0]
-    on_dev = _is_dev(columns[0])
-    assert all(c.shape[0] == n and _is_dev(c) == on_dev for c in columns), "columns share one size and placement"
-    if out is None:
-        out = _like(columns[0], n_outputs * n)
-    table = (ctypes.c_void_p * len(columns))(*[_p(c) for c in columns])
-    cfg = vec_config(is_a_on_device=on_dev, is_b_on_device=_is_dev(constants), is_result_on_device=_is_dev(out),
-                     is_async=is_async, stream=stream)
-    check(lib().mbls_fr_eval_program(table, len(columns), n, rot_stride, _p(constants),
-                                     0 if constants is None else constants.shape[0], _expr_program(program), len(program),
-                                     n_outputs, ctypes.byref(cfg), _p(out)), "mbls_fr_eval_program")
-    return out
+    return _eval_rows(lib().mbls_fr_eval_program, "mbls_fr_eval_program", _expr_program(program), len(program), columns,
+                      constants, n_outputs, rot_stride, out, stream, is_async)
 
 
 # ----------------------------------------------------------------------------- graph evaluator
@@ -847,18 +845,8 @@ def eval_graph(columns, program, *, constants=None, n_outputs=1, rot_stride=1, o
     """Run `program`, a list of (op, a, b, c) tuples of GRAPH_* opcodes whose a and b are (kind, idx, rot)
     sources, once per row (mbls_fr_eval_graph); op k defines value k.  columns, constants, out and the
     result are as eval_program's."""
-    n = columns[0].shape[0]
-    on_dev = _is_dev(columns[0])
-    assert all(c.shape[0] == n and _is_dev(c) == on_dev for c in columns), "columns share one size and placement"
-    if out is None:
-        out = _like(columns[0], n_outputs * n)
-    table = (ctypes.c_void_p * len(columns))(*[_p(c) for c in columns])
-    cfg = vec_config(is_a_on_device=on_dev, is_b_on_device=_is_dev(constants), is_result_on_device=_is_dev(out),
-                     is_async=is_async, stream=stream)
-    check(lib().mbls_fr_eval_graph(table, len(columns), n, rot_stride, _p(constants),
-                                   0 if constants is None else constants.shape[0], _graph_program(program), len(program),
-                                   n_outputs, ctypes.byref(cfg), _p(out)), "mbls_fr_eval_graph")
-    return out
+    return _eval_rows(lib().mbls_fr_eval_graph, "mbls_fr_eval_graph", _graph_program(program), len(program), columns,
+                      constants, n_outputs, rot_stride, out, stream, is_async)
 
 
 # ----------------------------------------------------------------------------- NTT

@@ -93,7 +93,7 @@ void* Arena::take(size_t bytes) {
 eIcicleError Staging::open() {
     if (n_ > MAX_BLOCKS) return MBLS_INVALID_ARGUMENT;
     size_t sum = 0;
-    for (int i = 0; i < n_; ++i) sum += align_up(blocks_[i].bytes);
+    for (int i = 0; i < n_; ++i) sum += align_up(blocks_[i].bytes) * (size_t)blocks_[i].count;
     if (!always_ && !sum) return MBLS_SUCCESS;
     lease_.emplace(st_);
     if (!*lease_) return lease_->error();
@@ -101,8 +101,14 @@ eIcicleError Staging::open() {
     if (er != MBLS_SUCCESS) return er;
     for (int i = 0; i < n_; ++i) {
         const Block& b = blocks_[i];
-        *b.p = static_cast<uint8_t*>((*lease_)->arena.take(b.bytes));
-        if (b.kind == IN) MBLS_TRY(hipMemcpyAsync(*b.p, b.host, b.bytes, hipMemcpyHostToDevice, st_));
+        const size_t col_stride = align_up(b.bytes);
+        uint8_t* at = static_cast<uint8_t*>((*lease_)->arena.take(col_stride * (size_t)b.count));
+        for (int k = 0; k < b.count; ++k, at += col_stride) {
+            b.p[k] = at;
+            if (b.kind == IN) MBLS_TRY(hipMemcpyAsync(at, b.host, b.bytes, hipMemcpyHostToDevice, st_));
+            if (b.kind == TABLE)
+                MBLS_TRY(hipMemcpyAsync(at, static_cast<void* const*>(b.host)[k], b.bytes, hipMemcpyHostToDevice, st_));
+        }
     }
     return MBLS_SUCCESS;
 }

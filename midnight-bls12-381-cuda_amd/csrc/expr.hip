@@ -26,15 +26,13 @@
 #include <utility>
 #include <vector>
 
-#include "mbls_common.hpp"
-#include "mbls_field.hpp"
+#include "mbls_rowprog.hpp"
 
 namespace mbls {
 
 static constexpr int EXPR_THREADS = 256;
 static constexpr int EXPR_MAX_OPS = 4096, EXPR_MAX_COLUMNS = 1024, EXPR_MAX_CONSTANTS = 1024;
 static constexpr int EXPR_MAX_OUTPUTS = 8, EXPR_MAX_DEPTH = 8;
-static constexpr size_t EXPR_MAX_ROWS = (size_t)1 << 26;
 static constexpr size_t EXPR_SLOT_BYTES = 32 * (size_t)EXPR_THREADS;  // one stack slot of a workgroup
 static constexpr int EXPR_MAX_GRID = 256 * 8;  // 8 workgroups per CU is the residency limit; stride beyond
 
@@ -45,17 +43,6 @@ struct ExprOp {
     const uint8_t* p;  // COLUMN: the column; CONST, SCALE, HORNER: the constant; EMIT: the output member
 };
 static_assert(sizeof(ExprOp) == 16, "one 16-byte fetch per op");
-
-MBLS_DEV void stack_put(uint32_t* sh, uint32_t slot, const Fr& v) {
-#pragma unroll
-    for (int w = 0; w < 8; ++w) sh[(slot * 8 + w) * EXPR_THREADS + threadIdx.x] = v.v[w];
-}
-MBLS_DEV Fr stack_get(const uint32_t* sh, uint32_t slot) {
-    Fr r;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) r.v[w] = sh[(slot * 8 + w) * EXPR_THREADS + threadIdx.x];
-    return r;
-}
 
 __global__ __launch_bounds__(EXPR_THREADS) void k_expr(const ExprOp* __restrict__ ops, uint32_t n_ops, uint32_t size,
                                                        uint32_t tiles) {
@@ -73,22 +60,22 @@ __global__ __launch_bounds__(EXPR_THREADS) void k_expr(const ExprOp* __restrict_
             case MBLS_EXPR_COLUMN: {
                 uint32_t j = i + o.off;  // < 2 size <= 2^27
                 j -= j >= size ? size : 0;
-                if (d) stack_put(sh, d - 1, top);
+                if (d) slot_put<EXPR_THREADS>(sh, d - 1, top);
                 top = load<FrCfg>(o.p + 32 * (size_t)j);
                 break;
             }
             case MBLS_EXPR_CONST:
-                if (d) stack_put(sh, d - 1, top);
+                if (d) slot_put<EXPR_THREADS>(sh, d - 1, top);
                 top = load<FrCfg>(o.p);
                 break;
             case MBLS_EXPR_ADD:
-                top = stack_get(sh, d - 2) + top;
+                top = slot_get<EXPR_THREADS>(sh, d - 2) + top;
                 break;
             case MBLS_EXPR_SUB:
-                top = stack_get(sh, d - 2) - top;
+                top = slot_get<EXPR_THREADS>(sh, d - 2) - top;
                 break;
             case MBLS_EXPR_MUL:
-                top = stack_get(sh, d - 2) * top;
+                top = slot_get<EXPR_THREADS>(sh, d - 2) * top;
                 break;
             case MBLS_EXPR_NEG:
                 top = neg(top);
@@ -103,11 +90,11 @@ __global__ __launch_bounds__(EXPR_THREADS) void k_expr(const ExprOp* __restrict_
                 top = top * load<FrCfg>(o.p);
                 break;
             case MBLS_EXPR_HORNER:
-                top = stack_get(sh, d - 2) * load<FrCfg>(o.p) + top;
+                top = slot_get<EXPR_THREADS>(sh, d - 2) * load<FrCfg>(o.p) + top;
                 break;
             default:  // MBLS_EXPR_EMIT: the host admits no other opcode
                 if (live) store<FrCfg>(const_cast<uint8_t*>(o.p) + 32 * (size_t)row, top);
-                if (d > 1) top = stack_get(sh, d - 2);
+                if (d > 1) top = slot_get<EXPR_THREADS>(sh, d - 2);
                 break;
             }
         }
@@ -190,6 +177,55 @@ static eIcicleError expr_check(const mbls_fr_expr_op* prog, int n_ops, int n_col
     return MBLS_SUCCESS;
 }
 
+// the evaluator's parts of the eval entry (rowprog_eval): the stack simulation, and an op resolved
+// with the depth the ops before it leave
+struct ExprEval {
+    using Src = mbls_fr_expr_op;
+    using Op = ExprOp;
+    static constexpr int THREADS = EXPR_THREADS, MAX_GRID = EXPR_MAX_GRID, MAX_COLUMNS = EXPR_MAX_COLUMNS;
+    static constexpr auto kernel = k_expr;
+    ExprInfo info;
+    int d = 0;  // the depth before the next op to resolve
+
+    eIcicleError check(const Src* prog, int n_ops, int n_columns, int n_constants, int n_outputs) {
+        return expr_check(prog, n_ops, n_columns, n_constants, n_outputs, &info);
+    }
+    size_t lds() const { return EXPR_SLOT_BYTES * (size_t)(info.depth - 1); }  // <= 56 KiB
+    Op resolve(int, const Src& o, const RowProgAddr& at) {
+        Op q = {(uint32_t)o.op | (uint32_t)d << 8, 0, nullptr};
+        switch (o.op) {
+        case MBLS_EXPR_COLUMN:
+            q.off = rowprog_offset(o.b, at.rot_stride, at.size);
+            q.p = at.columns[o.a];
+            ++d;
+            break;
+        case MBLS_EXPR_CONST:
+            q.p = at.constants + 32 * (size_t)o.a;
+            ++d;
+            break;
+        case MBLS_EXPR_SCALE:
+            q.p = at.constants + 32 * (size_t)o.a;
+            break;
+        case MBLS_EXPR_HORNER:
+            q.p = at.constants + 32 * (size_t)o.a;
+            --d;
+            break;
+        case MBLS_EXPR_EMIT:
+            q.p = at.output + at.col_bytes * (size_t)o.a;
+            --d;
+            break;
+        case MBLS_EXPR_ADD:
+        case MBLS_EXPR_SUB:
+        case MBLS_EXPR_MUL:
+            --d;
+            break;
+        default:  // NEG, DOUBLE, SQUARE: the depth stays
+            break;
+        }
+        return q;
+    }
+};
+
 }  // namespace mbls
 
 using namespace mbls;
@@ -212,82 +248,8 @@ eIcicleError mbls_fr_expr_check(const mbls_fr_expr_op* program, int n_ops, int n
 eIcicleError mbls_fr_eval_program(const mbls_fr_t* const* columns, int n_columns, size_t size, size_t rot_stride,
                                   const mbls_fr_t* constants, int n_constants, const mbls_fr_expr_op* program, int n_ops,
                                   int n_outputs, const VecOpsConfig* config, mbls_fr_t* output) {
-    if (!columns || !program || !config || !output || (!constants && n_constants > 0)) return MBLS_INVALID_POINTER;
-    if (size == 0 || size > EXPR_MAX_ROWS || rot_stride == 0 || rot_stride > EXPR_MAX_ROWS) return MBLS_INVALID_ARGUMENT;
-    ExprInfo info;
-    eIcicleError er = expr_check(program, n_ops, n_columns, n_constants, n_outputs, &info);
-    if (er != MBLS_SUCCESS) return er;
-    for (int k = 0; k < n_columns; ++k)
-        if (!columns[k]) return MBLS_INVALID_POINTER;
-    hipStream_t st = static_cast<hipStream_t>(config->stream);
-    const size_t col_bytes = 32 * size, col_stride = align_up(col_bytes);
-    const bool host_cols = !config->is_a_on_device;
-
-    Staging S(st, Staging::LEASE_ALWAYS);
-    uint8_t *dprog, *dcols = nullptr, *dout;
-    const uint8_t* dconst = nullptr;
-    S.scratch(&dprog, sizeof(ExprOp) * (size_t)n_ops);
-    if (host_cols) S.scratch(&dcols, col_stride * (size_t)n_columns);
-    if (n_constants > 0) S.in(&dconst, constants, 32 * (size_t)n_constants, config->is_b_on_device);
-    S.out(&dout, output, col_bytes * (size_t)n_outputs, config->is_result_on_device);
-    er = S.open();
-    if (er != MBLS_SUCCESS) return er;
-    if (host_cols)
-        for (int k = 0; k < n_columns; ++k)
-            MBLS_TRY(hipMemcpyAsync(dcols + col_stride * (size_t)k, columns[k], col_bytes, hipMemcpyHostToDevice, st));
-
-    // the resolved program; the copy leaves pageable memory before hipMemcpyAsync returns, as the
-    // staged operands do, so the buffer is the thread's own and is reused by its next call
-    static thread_local std::vector<ExprOp> resolved;
-    resolved.resize((size_t)n_ops);
-    int d = 0;
-    for (int k = 0; k < n_ops; ++k) {
-        const mbls_fr_expr_op& o = program[k];
-        ExprOp& q = resolved[(size_t)k];
-        q.op = (uint32_t)o.op | (uint32_t)d << 8;
-        q.off = 0;
-        q.p = nullptr;
-        switch (o.op) {
-        case MBLS_EXPR_COLUMN: {
-            // |b * rot_stride| < 2^31 * 2^26: 64 bits hold it
-            const int64_t m = (int64_t)size, t = (int64_t)o.b * (int64_t)rot_stride % m;
-            q.off = (uint32_t)(t < 0 ? t + m : t);
-            q.p = host_cols ? dcols + col_stride * (size_t)o.a : reinterpret_cast<const uint8_t*>(columns[o.a]);
-            ++d;
-            break;
-        }
-        case MBLS_EXPR_CONST:
-            q.p = dconst + 32 * (size_t)o.a;
-            ++d;
-            break;
-        case MBLS_EXPR_SCALE:
-            q.p = dconst + 32 * (size_t)o.a;
-            break;
-        case MBLS_EXPR_HORNER:
-            q.p = dconst + 32 * (size_t)o.a;
-            --d;
-            break;
-        case MBLS_EXPR_EMIT:
-            q.p = dout + col_bytes * (size_t)o.a;
-            --d;
-            break;
-        case MBLS_EXPR_ADD:
-        case MBLS_EXPR_SUB:
-        case MBLS_EXPR_MUL:
-            --d;
-            break;
-        default:  // NEG, DOUBLE, SQUARE: the depth stays
-            break;
-        }
-    }
-    MBLS_TRY(hipMemcpyAsync(dprog, resolved.data(), sizeof(ExprOp) * (size_t)n_ops, hipMemcpyHostToDevice, st));
-
-    const uint32_t tiles = (uint32_t)((size + EXPR_THREADS - 1) / EXPR_THREADS);
-    const size_t lds = EXPR_SLOT_BYTES * (size_t)(info.depth - 1);  // <= 56 KiB
-    hipLaunchKernelGGL(k_expr, dim3(std::min<uint32_t>(tiles, EXPR_MAX_GRID)), dim3(EXPR_THREADS), lds, st,
-                       reinterpret_cast<const ExprOp*>(dprog), (uint32_t)n_ops, (uint32_t)size, tiles);
-    MBLS_TRY(hipGetLastError());
-    return S.close(config->is_async);
+    return rowprog_eval<ExprEval>(columns, n_columns, size, rot_stride, constants, n_constants, program, n_ops, n_outputs,
+                                  config, output);
 }
 
 }  // extern "C"

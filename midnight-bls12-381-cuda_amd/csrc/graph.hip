@@ -27,9 +27,8 @@
 #include <algorithm>
 #include <vector>
 
-#include "mbls_common.hpp"
-#include "mbls_field.hpp"
 #include "mbls_graph.hpp"
+#include "mbls_rowprog.hpp"
 
 namespace mbls {
 
@@ -47,17 +46,6 @@ struct GraphOp {
     const uint8_t* pc;       // HORNER: the constant; EMIT: the output member
 };
 static_assert(sizeof(GraphOp) == 40, "ten dwords, fetched uniformly");
-
-MBLS_DEV void slot_put(uint32_t* sh, uint32_t slot, const Fr& v) {
-#pragma unroll
-    for (int w = 0; w < 8; ++w) sh[(slot * 8 + w) * GRAPH_THREADS + threadIdx.x] = v.v[w];
-}
-MBLS_DEV Fr slot_get(const uint32_t* sh, uint32_t slot) {
-    Fr r;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) r.v[w] = sh[(slot * 8 + w) * GRAPH_THREADS + threadIdx.x];
-    return r;
-}
 
 // Every address in a resolved op is device memory: the column and output accesses are told so, since
 // the generic (flat) form of a pointer read out of a struct also counts against the LDS counter and
@@ -94,7 +82,7 @@ MBLS_DEV Fr graph_operand(uint32_t from, uint32_t slot, uint32_t off, const uint
     case GRAPH_FROM_PREV:
         return prev;
     case GRAPH_FROM_SLOT:
-        return slot_get(sh, slot);
+        return slot_get<GRAPH_THREADS>(sh, slot);
     case GRAPH_FROM_COLUMN: {
         uint32_t j = i + off;  // < 2 size <= 2^27
         j -= j >= size ? size : 0;
@@ -150,11 +138,53 @@ __global__ __launch_bounds__(GRAPH_THREADS) void k_graph(const GraphOp* __restri
                 if (live) store_output(const_cast<uint8_t*>(o.pc) + 32 * (size_t)row, a);
                 continue;
             }
-            if (o.ctl >> 16 & 1) slot_put(sh, o.slots >> 16 & 0xff, r);
+            if (o.ctl >> 16 & 1) slot_put<GRAPH_THREADS>(sh, o.slots >> 16 & 0xff, r);
             prev = r;
         }
     }
 }
+
+// the evaluator's parts of the eval entry (rowprog_eval): mbls_graph.hpp's rules and slot
+// assignment, and an op resolved with its placement
+struct GraphEval {
+    using Src = mbls_fr_graph_op;
+    using Op = GraphOp;
+    static constexpr int THREADS = GRAPH_THREADS, MAX_GRID = GRAPH_MAX_GRID, MAX_COLUMNS = GRAPH_MAX_COLUMNS;
+    static constexpr auto kernel = k_graph;
+    GraphInfo info;
+    const GraphPlaced* placed;
+
+    eIcicleError check(const Src* prog, int n_ops, int n_columns, int n_constants, int n_outputs) {
+        static thread_local std::vector<GraphPlaced> buf;  // the thread's own, reused by its next call
+        const eIcicleError er = graph_check(prog, n_ops, n_columns, n_constants, n_outputs, &info, &buf);
+        placed = buf.data();
+        return er;
+    }
+    size_t lds() const { return GRAPH_SLOT_BYTES * (size_t)info.peak; }  // <= 64 KiB
+    Op resolve(int k, const Src& o, const RowProgAddr& at) const {
+        const GraphPlaced& p = placed[k];
+        Op q;
+        q.ctl = (uint32_t)p.op | (uint32_t)p.a_from << 8 | (uint32_t)p.b_from << 12 | (uint32_t)p.put << 16;
+        q.slots = (uint32_t)p.a_slot | (uint32_t)p.b_slot << 8 | (uint32_t)p.put_slot << 16;
+        const mbls_fr_graph_src* src[2] = {&o.a, &o.b};
+        uint32_t off[2] = {0, 0};
+        const uint8_t* ptr[2] = {nullptr, nullptr};
+        for (int s = 0; s < 2; ++s) {
+            const mbls_fr_graph_src& v = *src[s];
+            if (v.kind == MBLS_GRAPH_COLUMN) {
+                off[s] = rowprog_offset(v.rot, at.rot_stride, at.size);
+                ptr[s] = at.columns[v.idx];
+            } else if (v.kind == MBLS_GRAPH_CONST) {
+                ptr[s] = at.constants + 32 * (size_t)v.idx;
+            }
+        }
+        q.a_off = off[0], q.b_off = off[1], q.pa = ptr[0], q.pb = ptr[1];
+        q.pc =o.op == MBLS_GRAPH_HORNER ? at.constants + 32 * (size_t)o.c
+               : o.op == MBLS_GRAPH_EMIT ? at.output + at.col_bytes * (size_t)o.c
+                                         : nullptr;
+        return q;
+    }
+};
 
 }  // namespace mbls
 
@@ -182,69 +212,8 @@ eIcicleError mbls_fr_graph_check(const mbls_fr_graph_op* program, int n_ops, int
 eIcicleError mbls_fr_eval_graph(const mbls_fr_t* const* columns, int n_columns, size_t size, size_t rot_stride,
                                 const mbls_fr_t* constants, int n_constants, const mbls_fr_graph_op* program, int n_ops,
                                 int n_outputs, const VecOpsConfig* config, mbls_fr_t* output) {
-    if (!columns || !program || !config || !output || (!constants && n_constants > 0)) return MBLS_INVALID_POINTER;
-    if (size == 0 || size > GRAPH_MAX_ROWS || rot_stride == 0 || rot_stride > GRAPH_MAX_ROWS) return MBLS_INVALID_ARGUMENT;
-    GraphInfo info;
-    // the thread's own buffers, reused by its next call
-    static thread_local std::vector<GraphPlaced> placed;
-    static thread_local std::vector<GraphOp> resolved;
-    eIcicleError er = graph_check(program, n_ops, n_columns, n_constants, n_outputs, &info, &placed);
-    if (er != MBLS_SUCCESS) return er;
-    for (int k = 0; k < n_columns; ++k)
-        if (!columns[k]) return MBLS_INVALID_POINTER;
-    hipStream_t st = static_cast<hipStream_t>(config->stream);
-    const size_t col_bytes = 32 * size, col_stride = align_up(col_bytes);
-    const bool host_cols = !config->is_a_on_device;
-
-    Staging S(st, Staging::LEASE_ALWAYS);
-    uint8_t *dprog, *dcols = nullptr, *dout;
-    const uint8_t* dconst = nullptr;
-    S.scratch(&dprog, sizeof(GraphOp) * (size_t)n_ops);
-    if (host_cols) S.scratch(&dcols, col_stride * (size_t)n_columns);
-    if (n_constants > 0) S.in(&dconst, constants, 32 * (size_t)n_constants, config->is_b_on_device);
-    S.out(&dout, output, col_bytes * (size_t)n_outputs, config->is_result_on_device);
-    er = S.open();
-    if (er != MBLS_SUCCESS) return er;
-    if (host_cols)
-        for (int k = 0; k < n_columns; ++k)
-            MBLS_TRY(hipMemcpyAsync(dcols + col_stride * (size_t)k, columns[k], col_bytes, hipMemcpyHostToDevice, st));
-
-    // the resolved program; the copy leaves pageable memory before hipMemcpyAsync returns, as the
-    // staged operands do
-    resolved.resize((size_t)n_ops);
-    for (int k = 0; k < n_ops; ++k) {
-        const mbls_fr_graph_op& o = program[k];
-        const GraphPlaced& p = placed[(size_t)k];
-        GraphOp& q = resolved[(size_t)k];
-        q.ctl = (uint32_t)p.op | (uint32_t)p.a_from << 8 | (uint32_t)p.b_from << 12 | (uint32_t)p.put << 16;
-        q.slots = (uint32_t)p.a_slot | (uint32_t)p.b_slot << 8 | (uint32_t)p.put_slot << 16;
-            const mbls_fr_graph_src* src[2] = {&o.a, &o.b};
-        uint32_t off[2] = {0, 0};
-        const uint8_t* ptr[2] = {nullptr, nullptr};
-        for (int s = 0; s < 2; ++s) {
-            const mbls_fr_graph_src& v = *src[s];
-            if (v.kind == MBLS_GRAPH_COLUMN) {
-                // |rot * rot_stride| < 2^31 * 2^26: 64 bits hold it
-                const int64_t m = (int64_t)size, t = (int64_t)v.rot * (int64_t)rot_stride % m;
-                off[s] = (uint32_t)(t < 0 ? t + m : t);
-                ptr[s] = host_cols ? dcols + col_stride * (size_t)v.idx : reinterpret_cast<const uint8_t*>(columns[v.idx]);
-            } else if (v.kind == MBLS_GRAPH_CONST) {
-                ptr[s] = dconst + 32 * (size_t)v.idx;
-            }
-        }
-        q.a_off = off[0], q.b_off = off[1], q.pa = ptr[0], q.pb = ptr[1];
-        q.pc = o.op == MBLS_GRAPH_HORNER ? dconst + 32 * (size_t)o.c
-               : o.op == MBLS_GRAPH_EMIT ? dout + col_bytes * (size_t)o.c
-                                         : nullptr;
-    }
-    MBLS_TRY(hipMemcpyAsync(dprog, resolved.data(), sizeof(GraphOp) * (size_t)n_ops, hipMemcpyHostToDevice, st));
-
-    const uint32_t tiles = (uint32_t)((size + GRAPH_THREADS - 1) / GRAPH_THREADS);
-    const size_t lds = GRAPH_SLOT_BYTES * (size_t)info.peak;  // <= 64 KiB
-    hipLaunchKernelGGL(k_graph, dim3(std::min<uint32_t>(tiles, GRAPH_MAX_GRID)), dim3(GRAPH_THREADS), lds, st,
-                       reinterpret_cast<const GraphOp*>(dprog), (uint32_t)n_ops, (uint32_t)size, tiles);
-    MBLS_TRY(hipGetLastError());
-    return S.close(config->is_async);
+    return rowprog_eval<GraphEval>(columns, n_columns, size, rot_stride, constants, n_constants, program, n_ops, n_outputs,
+                                   config, output);
 }
 
 }  // extern "C"

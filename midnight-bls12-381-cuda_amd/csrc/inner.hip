@@ -298,14 +298,6 @@ static eIcicleError inner_launch(const std::vector<const uint8_t*>& ptrs, int n_
     return MBLS_SUCCESS;
 }
 
-static eIcicleError inner_check_table(const mbls_fr_t* const* table, int n, int max_n) {
-    if (!table) return MBLS_INVALID_POINTER;
-    if (n < 1 || n > max_n) return MBLS_INVALID_ARGUMENT;
-    for (int k = 0; k < n; ++k)
-        if (!table[k]) return MBLS_INVALID_POINTER;
-    return MBLS_SUCCESS;
-}
-
 }  // namespace mbls
 
 using namespace mbls;
@@ -316,37 +308,24 @@ eIcicleError mbls_fr_inner_products(const mbls_fr_t* const* columns, int n_colum
                                     int n_vectors, size_t size, const VecOpsConfig* config, mbls_fr_t* output) {
     if (!columns || !vectors || !config || !output) return MBLS_INVALID_POINTER;
     if (size == 0 || size > INNER_MAX_ROWS) return MBLS_INVALID_ARGUMENT;
-    eIcicleError er = inner_check_table(columns, n_columns, INNER_MAX_COLUMNS);
+    eIcicleError er = check_table(columns, n_columns, INNER_MAX_COLUMNS);
     if (er != MBLS_SUCCESS) return er;
-    er = inner_check_table(vectors, n_vectors, INNER_MAX_VECTORS);
+    er = check_table(vectors, n_vectors, INNER_MAX_VECTORS);
     if (er != MBLS_SUCCESS) return er;
     hipStream_t st = static_cast<hipStream_t>(config->stream);
     const InnerGeom g = inner_geom(size, n_columns, n_vectors);
-    const size_t col_bytes = 32 * size, col_stride = align_up(col_bytes);
-    const bool host_cols = !config->is_a_on_device, host_vecs = !config->is_b_on_device;
-    const size_t staged = (host_cols ? (size_t)n_columns : 0) + (host_vecs ? (size_t)n_vectors : 0);
+    static thread_local std::vector<const uint8_t*> ptrs;
+    ptrs.resize((size_t)(n_columns + n_vectors));
 
     Staging S(st, Staging::LEASE_ALWAYS);
     uint8_t *scratch, *dout;
-    // one block: the partial sums, the pointer tables, then the staged host columns and vectors
-    S.scratch(&scratch, g.partial_bytes + g.table_bytes + col_stride * staged);
+    // the partial sums, then the pointer tables
+    S.scratch(&scratch, g.partial_bytes + g.table_bytes);
+    S.in_table(ptrs.data(), columns, n_columns, 32 * size, config->is_a_on_device);
+    S.in_table(ptrs.data() + n_columns, vectors, n_vectors, 32 * size, config->is_b_on_device);
     S.out(&dout, output, 32 * (size_t)n_columns * (size_t)n_vectors, config->is_result_on_device);
     er = S.open();
     if (er != MBLS_SUCCESS) return er;
-    uint8_t* stage = scratch + g.partial_bytes + g.table_bytes;
-    static thread_local std::vector<const uint8_t*> ptrs;
-    ptrs.clear();
-    for (int k = 0; k < n_columns + n_vectors; ++k) {
-        const bool is_col = k < n_columns;
-        const void* src = is_col ? columns[k] : vectors[k - n_columns];
-        if (is_col ? host_cols : host_vecs) {
-            MBLS_TRY(hipMemcpyAsync(stage, src, col_bytes, hipMemcpyHostToDevice, st));
-            ptrs.push_back(stage);
-            stage += col_stride;
-        } else {
-            ptrs.push_back(static_cast<const uint8_t*>(src));
-        }
-    }
     er = inner_launch(ptrs, n_columns, n_vectors, size, g, scratch + g.partial_bytes, scratch, dout, st);
     if (er != MBLS_SUCCESS) return er;
     return S.close(config->is_async);
@@ -356,22 +335,21 @@ eIcicleError mbls_fr_multi_eval(const mbls_fr_t* const* columns, int n_columns, 
                                 int n_points, const VecOpsConfig* config, mbls_fr_t* output) {
     if (!columns || !points || !config || !output) return MBLS_INVALID_POINTER;
     if (size == 0 || size > INNER_MAX_ROWS) return MBLS_INVALID_ARGUMENT;
-    eIcicleError er = inner_check_table(columns, n_columns, INNER_MAX_COLUMNS);
+    eIcicleError er = check_table(columns, n_columns, INNER_MAX_COLUMNS);
     if (er != MBLS_SUCCESS) return er;
     if (n_points < 1 || n_points > INNER_MAX_VECTORS) return MBLS_INVALID_ARGUMENT;
     hipStream_t st = static_cast<hipStream_t>(config->stream);
     const InnerGeom g = inner_geom(size, n_columns, n_points);
-    const size_t col_bytes = 32 * size, col_stride = align_up(col_bytes);
-    const bool host_cols = !config->is_a_on_device;
-    const size_t tab_bytes = inner_pow_table_bytes(g, (size_t)n_points), pow_bytes = align_up(col_bytes * (size_t)n_points);
+    const size_t col_bytes = 32 * size, tab_bytes = inner_pow_table_bytes(g, (size_t)n_points);
+    static thread_local std::vector<const uint8_t*> ptrs;
+    ptrs.resize((size_t)(n_columns + n_points));
 
     Staging S(st, Staging::LEASE_ALWAYS);
     uint8_t *scratch, *dout;
     const uint8_t* dpoints;
-    // one block: the partial sums, the pointer tables, the power tables, the powers of every point,
-    // then the staged host columns
-    S.scratch(&scratch, g.partial_bytes + g.table_bytes + tab_bytes + pow_bytes +
-                            (host_cols ? col_stride * (size_t)n_columns : 0));
+    // the partial sums, the pointer tables, the power tables, then the powers of every point
+    S.scratch(&scratch, g.partial_bytes + g.table_bytes + tab_bytes + align_up(col_bytes * (size_t)n_points));
+    S.in_table(ptrs.data(), columns, n_columns, col_bytes, config->is_a_on_device);
     S.in(&dpoints, points, 32 * (size_t)n_points, config->is_b_on_device);
     S.out(&dout, output, 32 * (size_t)n_columns * (size_t)n_points, config->is_result_on_device);
     er = S.open();
@@ -379,21 +357,9 @@ eIcicleError mbls_fr_multi_eval(const mbls_fr_t* const* columns, int n_columns, 
     uint8_t* dtab = scratch + g.partial_bytes;
     uint8_t* ptab = dtab + g.table_bytes;
     uint8_t* pw = ptab + tab_bytes;
-    uint8_t* stage = pw + pow_bytes;
     // the powers of the points, a batch of n_points members: vector k starts at row k * size
     powers_launch(pw, ptab, dpoints, nullptr, size, (size_t)n_points, g, st);
-    static thread_local std::vector<const uint8_t*> ptrs;
-    ptrs.clear();
-    for (int k = 0; k < n_columns; ++k) {
-        if (host_cols) {
-            MBLS_TRY(hipMemcpyAsync(stage, columns[k], col_bytes, hipMemcpyHostToDevice, st));
-            ptrs.push_back(stage);
-            stage += col_stride;
-        } else {
-            ptrs.push_back(reinterpret_cast<const uint8_t*>(columns[k]));
-        }
-    }
-    for (int k = 0; k < n_points; ++k) ptrs.push_back(pw + col_bytes * (size_t)k);
+    for (int k = 0; k < n_points; ++k) ptrs[(size_t)(n_columns + k)] = pw + col_bytes * (size_t)k;
     er = inner_launch(ptrs, n_columns, n_points, size, g, dtab, scratch, dout, st);
     if (er != MBLS_SUCCESS) return er;
     return S.close(config->is_async);

@@ -177,14 +177,6 @@ static int logup_chunk(size_t n) {
     return chunk;
 }
 
-// the checks the pointer-table entries share, before any device work
-static eIcicleError logup_inputs(const mbls_fr_t* const* inputs, int n_inputs) {
-    if (n_inputs < 1 || n_inputs > LOGUP_MAX_INPUTS) return MBLS_INVALID_ARGUMENT;
-    for (int c = 0; c < n_inputs; ++c)
-        if (!inputs[c]) return MBLS_INVALID_POINTER;
-    return MBLS_SUCCESS;
-}
-
 }  // namespace mbls
 
 using namespace mbls;
@@ -198,36 +190,25 @@ eIcicleError mbls_fr_lookup_multiplicities(const mbls_fr_t* const* inputs, int n
     SortCall c;
     eIcicleError er = sort_call(size, config, &c);
     if (er != MBLS_SUCCESS) return er;
-    er = logup_inputs(inputs, n_inputs);
+    er = check_table(inputs, n_inputs, LOGUP_MAX_INPUTS);
     if (er != MBLS_SUCCESS) return er;
     hipStream_t st = static_cast<hipStream_t>(config->stream);
-    const size_t n = c.size * c.batch, col_bytes = 32 * n, col_stride = align_up(col_bytes);
+    const size_t n = c.size * c.batch, col_bytes = 32 * n;
     const SortGeom g = sort_geom(n);
     const SortLayout L = sort_layout(n, false, c.batch);
-    const bool host_cols = !config->is_a_on_device;
-    const size_t counts_at = L.bytes, counts_bytes = align_up(8 * (n + c.batch));
-    const size_t stage_at = counts_at + counts_bytes;
+    const size_t counts_at = L.bytes;
 
     Staging S(st, Staging::LEASE_ALWAYS);
     uint8_t *scratch, *dm;
-    // one block: the sort's, the counts (rows, then the members' missing cells), the staged operands
-    S.scratch(&scratch, stage_at + (host_cols ? col_stride * (size_t)(n_inputs + 1) : 0));
+    const uint8_t* dtab;
+    LogupCols cols{};
+    // the sort's, then the counts (rows, then the members' missing cells)
+    S.scratch(&scratch, counts_at + align_up(8 * (n + c.batch)));
+    S.in(&dtab, table, col_bytes, config->is_a_on_device);
+    S.in_table(cols.p, inputs, n_inputs, col_bytes, config->is_a_on_device);
     S.out(&dm, multiplicities, col_bytes, config->is_result_on_device);
     er = S.open();
     if (er != MBLS_SUCCESS) return er;
-    LogupCols cols{};
-    const uint8_t* dtab = reinterpret_cast<const uint8_t*>(table);
-    for (int k = 0; k < n_inputs; ++k) cols.p[k] = reinterpret_cast<const uint8_t*>(inputs[k]);
-    if (host_cols) {
-        uint8_t* stage = scratch + stage_at;
-        MBLS_TRY(hipMemcpyAsync(stage, table, col_bytes, hipMemcpyHostToDevice, st));
-        dtab = stage;
-        for (int k = 0; k < n_inputs; ++k) {
-            uint8_t* to = stage + col_stride * (size_t)(k + 1);
-            MBLS_TRY(hipMemcpyAsync(to, inputs[k], col_bytes, hipMemcpyHostToDevice, st));
-            cols.p[k] = to;
-        }
-    }
     const uint32_t* idx;
     er = sort_launch(g, c.size, scratch, L, dtab, nullptr, g.n, montgomery, st, &idx);
     if (er != MBLS_SUCCESS) return er;
@@ -281,41 +262,28 @@ eIcicleError mbls_fr_logup_sum(const mbls_fr_t* const* inputs, int n_inputs, con
     ScanCall c;
     eIcicleError er = scan_call(size, config, &c);
     if (er != MBLS_SUCCESS) return er;
-    er = logup_inputs(inputs, n_inputs);
+    er = check_table(inputs, n_inputs, LOGUP_MAX_INPUTS);
     if (er != MBLS_SUCCESS) return er;
     hipStream_t st = static_cast<hipStream_t>(config->stream);
     const size_t n = c.size * c.batch, bytes = 32 * n, stride = align_up(bytes), per_member = 32 * (size_t)c.batch;
     const size_t agg_bytes = align_up(per_member * c.g.groups);
-    const bool host_cols = !config->is_a_on_device;
-    const size_t stage_at = 2 * agg_bytes + 2 * stride;
 
     Staging S(st, Staging::LEASE_ALWAYS);
     uint8_t *scratch, *dout, *dtotal = nullptr;
-    const uint8_t *dbeta, *dinit = nullptr;
-    // one block: the span aggregates, the values entering the spans, the terms, the numerators, then
-    // the staged table, multiplicities and columns (the denominators live in the output)
-    S.scratch(&scratch, stage_at + (host_cols ? stride * (size_t)(n_inputs + 2) : 0));
+    const uint8_t *dtab, *dmult, *dbeta, *dinit = nullptr;
+    LogupCols cols{};
+    // the span aggregates, the values entering the spans, the terms, then the numerators (the
+    // denominators live in the output)
+    S.scratch(&scratch, 2 * agg_bytes + 2 * stride);
+    S.in(&dtab, table, bytes, config->is_a_on_device);
+    S.in(&dmult, multiplicities, bytes, config->is_a_on_device);
+    S.in_table(cols.p, inputs, n_inputs, bytes, config->is_a_on_device);
     S.in(&dbeta, beta, per_member, config->is_b_on_device);
     if (init) S.in(&dinit, init, per_member, config->is_b_on_device);
     S.out(&dout, output, bytes, config->is_result_on_device);
     if (total) S.out(&dtotal, total, per_member, config->is_result_on_device);
     er = S.open();
     if (er != MBLS_SUCCESS) return er;
-    LogupCols cols{};
-    const uint8_t *dtab = reinterpret_cast<const uint8_t*>(table), *dmult = reinterpret_cast<const uint8_t*>(multiplicities);
-    for (int k = 0; k < n_inputs; ++k) cols.p[k] = reinterpret_cast<const uint8_t*>(inputs[k]);
-    if (host_cols) {
-        uint8_t* stage = scratch + stage_at;
-        MBLS_TRY(hipMemcpyAsync(stage, table, bytes, hipMemcpyHostToDevice, st));
-        MBLS_TRY(hipMemcpyAsync(stage + stride, multiplicities, bytes, hipMemcpyHostToDevice, st));
-        dtab = stage;
-        dmult = stage + stride;
-        for (int k = 0; k < n_inputs; ++k) {
-            uint8_t* to = stage + stride * (size_t)(k + 2);
-            MBLS_TRY(hipMemcpyAsync(to, inputs[k], bytes, hipMemcpyHostToDevice, st));
-            cols.p[k] = to;
-        }
-    }
     uint8_t *agg = scratch, *carry = scratch + agg_bytes, *term = scratch + 2 * agg_bytes, *num = term + stride;
     const int chunk = logup_chunk(n);
     const size_t per_block = (size_t)256 * chunk;

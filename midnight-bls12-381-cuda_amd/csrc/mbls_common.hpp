@@ -110,8 +110,8 @@ void count_scratch_free(size_t bytes);
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 // Operand staging of one call on stream `st`.  The call declares its arena blocks in order --
-// scratch(), in(), out() -- then open()s: one lease, ONE reserve of the declared sum, the blocks
-// handed out in declaration order (into *p), the host inputs copied in.  A device operand is
+// scratch(), in(), in_table(), out() -- then open()s: one lease, ONE reserve of the declared sum, the
+// blocks handed out in declaration order (into *p), the host inputs copied in.  A device operand is
 // passed through (*p = the caller's pointer, no block).  close() copies the host outputs back and
 // synchronises unless the call is async with every output on the device.  The Staging object holds
 // the lease: it lives until the call's last enqueue.
@@ -126,6 +126,15 @@ class Staging {
         if (on_device) *p = static_cast<const uint8_t*>(src);
         else add(const_cast<uint8_t**>(p), const_cast<void*>(src), bytes, IN);
     }
+    // a table of n operands of `bytes` each, all on the host or all on the device: dptrs[k] is where
+    // the kernels read member k.  Host members share one block, member k at k * align_up(bytes);
+    // dptrs is the caller's array, filled at open() like the *p of the other blocks
+    template <class T>
+    void in_table(const uint8_t** dptrs, const T* const* srcs, int n, size_t bytes, bool on_device) {
+        if (on_device)
+            for (int k = 0; k < n; ++k) dptrs[k] = reinterpret_cast<const uint8_t*>(srcs[k]);
+        else add(const_cast<uint8_t**>(dptrs), const_cast<T**>(srcs), bytes, TABLE, n);
+    }
     void out(uint8_t** p, void* dst, size_t bytes, bool on_device) {
         if (on_device) *p = static_cast<uint8_t*>(dst);
         else add(p, dst, bytes, OUT);
@@ -134,16 +143,17 @@ class Staging {
     eIcicleError close(bool is_async);
 
   private:
-    enum Kind { SCRATCH, IN, OUT };
+    enum Kind { SCRATCH, IN, TABLE, OUT };
     struct Block {
         uint8_t** p;
-        void* host;
-        size_t bytes;
+        void* host;    // TABLE: the caller's array of `count` host pointers
+        size_t bytes;  // TABLE: of one member
         Kind kind;
+        int count;
     };
-    static constexpr int MAX_BLOCKS = 6;
-    void add(uint8_t** p, void* host, size_t bytes, Kind kind) {
-        if (n_ < MAX_BLOCKS) blocks_[n_] = {p, host, bytes, kind};
+    static constexpr int MAX_BLOCKS = 8;  // mbls_fr_logup_sum with init and total, all on the host
+    void add(uint8_t** p, void* host, size_t bytes, Kind kind, int count = 1) {
+        if (n_ < MAX_BLOCKS) blocks_[n_] = {p, host, bytes, kind, count};
         ++n_;  // beyond MAX_BLOCKS: open() fails
     }
     hipStream_t st_;
@@ -152,6 +162,17 @@ class Staging {
     int n_ = 0;
     std::optional<CtxLease> lease_;
 };
+
+// The refusals of a caller's pointer table, in this order: no table INVALID_POINTER, a count outside
+// [1, max_n] INVALID_ARGUMENT, a null member INVALID_POINTER
+template <class T>
+eIcicleError check_table(const T* const* table, int n, int max_n) {
+    if (!table) return MBLS_INVALID_POINTER;
+    if (n < 1 || n > max_n) return MBLS_INVALID_ARGUMENT;
+    for (int k = 0; k < n; ++k)
+        if (!table[k]) return MBLS_INVALID_POINTER;
+    return MBLS_SUCCESS;
+}
 
 // is `p` a device (or managed) pointer?  Used only for defensive validation.
 bool is_device_pointer(const void* p);

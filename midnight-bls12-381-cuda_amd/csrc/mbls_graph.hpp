@@ -25,7 +25,6 @@ namespace mbls {
 static constexpr int GRAPH_MAX_OPS = 16384, GRAPH_MAX_COLUMNS = 1024, GRAPH_MAX_CONSTANTS = 1024;
 static constexpr int GRAPH_MAX_OUTPUTS = 8;
 static constexpr int GRAPH_BUDGET = 32;  // resident values: 32 slots of 2 KiB are the 64 KiB of one workgroup
-static constexpr size_t GRAPH_MAX_ROWS = (size_t)1 << 26;
 
 // where the kernel finds an operand
 enum GraphFrom : uint32_t { GRAPH_FROM_NONE = 0, GRAPH_FROM_PREV, GRAPH_FROM_SLOT, GRAPH_FROM_COLUMN, GRAPH_FROM_CONST };

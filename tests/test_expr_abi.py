@@ -85,6 +85,8 @@ def test_eval_program_refuses_before_any_device_work(built):
     col = (ctypes.c_uint64 * 8)()
     table = (ctypes.c_void_p * 2)(ctypes.addressof(col), ctypes.addressof(col))
     holed = (ctypes.c_void_p * 2)(ctypes.addressof(col), None)
+    full = (ctypes.c_void_p * 1025)(*[ctypes.addressof(col)] * 1025)
+    full[1023] = None
     ok = amd._expr_program([(E.COLUMN, 1, 0), (E.EMIT, 0, 0)])
     deep = amd._expr_program(T.MALFORMED["depth_9"][0])
     cfg = ctypes.byref(amd.vec_config())
@@ -103,6 +105,12 @@ def test_eval_program_refuses_before_any_device_work(built):
         (L.mbls_fr_eval_program(table, 2, 2, (1 << 26) + 1, None, 0, ok, 2, 1, cfg, out), A_),
         (L.mbls_fr_eval_program(table, 1, 2, 1, None, 0, ok, 2, 1, cfg, out), A_),  # column 1 of 1
         (L.mbls_fr_eval_program(table, 2, 2, 1, None, 0, deep, 18, 1, cfg, out), A_),
+        # a table of the most columns whose last is null: alone, then with a malformed program, no
+        # rows, one column too many -- the program, the size and the count are looked at first
+        (L.mbls_fr_eval_program(full, 1024, 2, 1, None, 0, ok, 2, 1, cfg, out), P),
+        (L.mbls_fr_eval_program(full, 1024, 2, 1, None, 0, deep, 18, 1, cfg, out), A_),
+        (L.mbls_fr_eval_program(full, 1024, 0, 1, None, 0, ok, 2, 1, cfg, out), A_),
+        (L.mbls_fr_eval_program(full, 1025, 2, 1, None, 0, ok, 2, 1, cfg, out), A_),
     ]
     for k, (got, want) in enumerate(cases):
         assert got == want, k

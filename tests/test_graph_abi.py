@@ -157,6 +157,8 @@ def test_eval_graph_refuses_before_any_device_work(built):
     col = (ctypes.c_uint64 * 8)()
     table = (ctypes.c_void_p * 2)(ctypes.addressof(col), ctypes.addressof(col))
     holed = (ctypes.c_void_p * 2)(ctypes.addressof(col), None)
+    full = (ctypes.c_void_p * 1025)(*[ctypes.addressof(col)] * 1025)
+    full[1023] = None
     ok = amd._graph_program([(G.NEG, G.col(1), G.NO, 0), T.X(G.val(0))])
     deep_prog = G.at_budget(G.BUDGET + 1)
     deep = amd._graph_program(deep_prog)
@@ -178,6 +180,12 @@ def test_eval_graph_refuses_before_any_device_work(built):
         (f(table, 1, 2, 1, None, 0, ok, 2, 1, cfg, out), A_),  # column 1 of 1
         (f(table, 2, 2, 1, None, 0, deep, len(deep_prog), 1, cfg, out), A_),  # column 3 of 2
         (f((ctypes.c_void_p * 4)(*[ctypes.addressof(col)] * 4), 4, 2, 1, None, 0, deep, len(deep_prog), 1, cfg, out), A_),
+        # a table of the most columns whose last is null: alone, then with a malformed program, no
+        # rows, one column too many -- the program, the size and the count are looked at first
+        (f(full, 1024, 2, 1, None, 0, ok, 2, 1, cfg, out), P),
+        (f(full, 1024, 2, 1, None, 0, deep, len(deep_prog), 1, cfg, out), A_),
+        (f(full, 1024, 0, 1, None, 0, ok, 2, 1, cfg, out), A_),
+        (f(full, 1025, 2, 1, None, 0, ok, 2, 1, cfg, out), A_),
     ]
     for k, (got, want) in enumerate(cases):
         assert got == want, k

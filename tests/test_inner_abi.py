@@ -60,7 +60,10 @@ def test_argument_errors_come_before_any_device_work(amd):
     cols = (ctypes.c_void_p * 1025)(*[P(col)] * 1025)
     vecs = (ctypes.c_void_p * 17)(*[P(col)] * 17)
     hole = (ctypes.c_void_p * 3)(P(col), None, P(col))
-    c = ctypes.byref(amd.vec_config())
+    hc = (ctypes.c_void_p * 1025)(*[P(col)] * 1025)  # the last of the most columns, of the most vectors, is null
+    hv = (ctypes.c_void_p * 17)(*[P(col)] * 17)
+    hc[1023] = hv[15] = None
+    c =ctypes.byref(amd.vec_config())
     c2 = ctypes.byref(amd.vec_config(batch_size=2))
     cb = ctypes.byref(amd.vec_config(batch_size=2, columns_batch=True))
     half = (1 << 25) + 1
@@ -91,6 +94,19 @@ def test_argument_errors_come_before_any_device_work(amd):
         (mev(cols, 1, 8, P(col), 17, c, P(out)), ARG),
         (mev(cols, 1, 0, P(col), 1, c, P(out)), ARG),
         (mev(cols, 1, MAX + 1, P(col), 1, c, P(out)), ARG),
+        # a full table whose last member is null: alone, then with no rows and with one member too
+        # many (both looked at first), then with a fault of the operand after it (looked at later)
+        (inner(hc, 1024, vecs, 1, 8, c, P(out)), PTR),
+        (inner(cols, 1, hv, 16, 8, c, P(out)), PTR),
+        (inner(hc, 1024, vecs, 1, 0, c, P(out)), ARG),
+        (inner(cols, 1, hv, 16, 0, c, P(out)), ARG),
+        (inner(hc, 1025, vecs, 1, 8, c, P(out)), ARG),
+        (inner(cols, 1, hv, 17, 8, c, P(out)), ARG),
+        (inner(hc, 1024, vecs, 17, 8, c, P(out)), PTR),
+        (mev(hc, 1024, 8, P(col), 1, c, P(out)), PTR),
+        (mev(hc, 1024, 0, P(col), 1, c, P(out)), ARG),
+        (mev(hc, 1025, 8, P(col), 1, c, P(out)), ARG),
+        (mev(hc, 1024, 8, P(col), 17, c, P(out)), PTR),
         (pw(None, None, 8, c, P(out)), PTR),
         (pw(P(col), None, 8, None, P(out)), PTR),
         (pw(P(col), P(col), 8, c, None), PTR),

@@ -61,6 +61,8 @@ def test_argument_errors_come_before_any_device_work(amd):
     cnt = (ctypes.c_uint64 * 2)()
     cols = (ctypes.c_void_p * 65)(*[P(col)] * 65)
     hole = (ctypes.c_void_p * 3)(P(col), None, P(col))
+    full = (ctypes.c_void_p * 65)(*[P(col)] * 65)  # the last of the most inputs is null
+    full[63] = None
     c = ctypes.byref(amd.vec_config())
     c2 = ctypes.byref(amd.vec_config(batch_size=2))
     cb = ctypes.byref(amd.vec_config(batch_size=2, columns_batch=True))
@@ -100,6 +102,14 @@ def test_argument_errors_come_before_any_device_work(amd):
         (lsum(cols, 1, P(tab), P(m), MAX + 1, P(one), None, c, P(out), None), ARG),
         (lsum(cols, 4, P(tab), P(m), half, P(one), P(one), c2, P(out), P(one)), ARG),
         (lsum(cols, 1, P(tab), P(m), 4, P(one), None, cb, P(out), None), NOT),
+        # a full table whose last member is null: alone, then with no rows and with one input too
+        # many, both of which are looked at first
+        (mult(full, 64, P(tab), 8, True, False, c, P(m), cnt), PTR),
+        (mult(full, 64, P(tab), 0, True, False, c, P(m), cnt), ARG),
+        (mult(full, 65, P(tab), 8, True, False, c, P(m), cnt), ARG),
+        (lsum(full, 64, P(tab), P(m), 8, P(one), None, c, P(out), None), PTR),
+        (lsum(full, 64, P(tab), P(m), 0, P(one), None, c, P(out), None), ARG),
+        (lsum(full, 65, P(tab), P(m), 8, P(one), None, c, P(out), None), ARG),
     ]
     for k, (got, want) in enumerate(cases):
         assert got == want, k
