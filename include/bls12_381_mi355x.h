@@ -687,6 +687,67 @@ eIcicleError mbls_g1_ecntt(const mbls_g1_affine_t* input, int size, NTTDir dir, 
                            mbls_g1_affine_t* output);
 
 /* ------------------------------------------------------------------------------------ */
+/* fixed-base batch multiplication: output[i] = [scalars[i] mod r] base for ONE base, and a KZG SRS
+ * from a secret (no reference counterpart; halo2's ParamsKZG::unsafe_setup computes g[i] =
+ * [s^i] G, g_lagrange[i] = [L_i(s)] G and s_g2 = [s] G2 this way).  The doublings are paid once, in
+ * a table of the base; a scalar then costs at most W mixed additions.
+ *   plan: mbls_fixed_base_plan(group, out) is host only; group 1 = G1, 2 = G2.  out[0] = c (digit
+ *     width), out[1] = windows W = ceil(255 / c), out[2] = entries per window = 2^(c-1), out[3] =
+ *     table entries = W * 2^(c-1), out[4] = bytes per entry (96 / 192), out[5] = lanes per
+ *     workgroup, out[6] = most lanes per launch (a larger batch runs as several launches over one
+ *     work array; 0 would mean no chunking), out[7] = scratch bytes per output point of a launch.
+ *   table: table[w * 2^(c-1) + (d-1)] = [d * 2^(c w)] base for d = 1..2^(c-1), canonical
+ *     Montgomery affine.  It is a caller-owned DEVICE buffer of out[3] entries; nothing is cached in
+ *     the library.  `base` is placed by is_a_on_device.  A base equal to the identity (all zero)
+ *     gives an all-zero table, and every product of it is the identity.  The base is ASSUMED to lie
+ *     in the order-r subgroup: the table build runs mbls_g*_scalar_mul (GLV / psi), and the
+ *     multiplication reduces k mod r.  The multiplication itself uses no endomorphism.
+ *   scalars: 32 bytes, any 256-bit value; reduced mod r first (Montgomery scalars, when
+ *     scalars_montgomery is set, go through from_mont first).  Placed by is_b_on_device.
+ *   output: canonical Montgomery AFFINE, identity = all zero, placed by is_result_on_device: a
+ *     result has exactly one byte representation.  Host operands are staged through the leased
+ *     scratch context, which also holds the Jacobian work array: no allocation per call once it is
+ *     large enough.  A host output is synchronous, a device output synchronises unless is_async
+ *     (as scalar_mul).  batch_size and columns_batch are not read.
+ *   mbls_fixed_base_recode (host only): the W signed digits of scalar mod r (standard form), lowest
+ *     window first, by the function the kernels run: digits in [-2^(c-1), 2^(c-1) - 1], the top
+ *     one in [0, 2^(c-1)], sum digits[w] 2^(c w) = scalar mod r.
+ *   mbls_g1_srs_from_secret: `tau` is ONE Montgomery element in HOST memory (as coset_gen is).
+ *     basis 0: output[i] = [tau^i] base, size in 1..2^26, 0^0 = 1.
+ *     basis 1: output[i] = [L_i(tau)] base, L_i(tau) = (tau^n - 1)/n * w^i / (tau - w^i), n = size =
+ *       2^k within the order of the initialised NTT domain (mbls_g1_ecntt's rule; 32 with none
+ *       initialised: no domain is needed), w the Fr NTT's root of that size.  The formula has a
+ *       pole where tau^n = 1 (halo2 panics): INVALID_ARGUMENT, decided on the host by k squarings.
+ *       It equals mbls_g1_ecntt(inverse) of basis 0, byte for byte, without an EC-NTT.
+ *     The scalars are made on the device (mbls_fr_powers, bls12_381_batch_inv_cuda, the vecops),
+ *     then one multiplication runs over them; `table` is that of the base.
+ *   The table build, the G2 normalisation and the SRS call run other entries of this library,
+ *   which lease a scratch context of their own while the call holds one.  A thread that already
+ *   holds a context never waits for a second: when none is free it gets one past
+ *   MBLS_SCRATCH_CONTEXTS, so these calls are safe from any number of threads and with any limit
+ *   (the pool then holds up to one context more per thread that is inside them at once).
+ *   errors, before any device work: INVALID_POINTER for a null table, base, scalars, tau, config,
+ *     output or plan / digit array; INVALID_ARGUMENT for size <= 0 or size > 2^26, a group other
+ *     than 1 or 2, a basis other than 0 or 1, and for basis 1 a size that is no power of two or
+ *     past the domain's order, and tau^size = 1.
+ *   timing: NOT constant time -- table addresses depend on the scalar's digits, and zero digits are
+ *     skipped.  Do not multiply a secret key, or the secret of a real ceremony, with these calls
+ *     where timing or cache behaviour is observable; they serve unsafe_setup, public scalars and
+ *     tests.  A ceremony SRS is read, decompressed and checked instead (mbls_g*_decompress,
+ *     mbls_g*_check_points).                                                                    */
+/* ------------------------------------------------------------------------------------ */
+eIcicleError mbls_fixed_base_plan(int group, int64_t* out);
+eIcicleError mbls_fixed_base_recode(const mbls_fr_t* scalar, int32_t* digits);
+eIcicleError mbls_g1_fixed_base_table(const mbls_g1_affine_t* base, const VecOpsConfig* config, mbls_g1_affine_t* table);
+eIcicleError mbls_g2_fixed_base_table(const mbls_g2_affine_t* base, const VecOpsConfig* config, mbls_g2_affine_t* table);
+eIcicleError mbls_g1_fixed_base_mul(const mbls_g1_affine_t* table, const mbls_fr_t* scalars, int size,
+                                    bool scalars_montgomery, const VecOpsConfig* config, mbls_g1_affine_t* output);
+eIcicleError mbls_g2_fixed_base_mul(const mbls_g2_affine_t* table, const mbls_fr_t* scalars, int size,
+                                    bool scalars_montgomery, const VecOpsConfig* config, mbls_g2_affine_t* output);
+eIcicleError mbls_g1_srs_from_secret(const mbls_g1_affine_t* table, const mbls_fr_t* tau, int size, int basis,
+                                     const VecOpsConfig* config, mbls_g1_affine_t* output);
+
+/* ------------------------------------------------------------------------------------ */
 /* batch point validation: is every point canonical, on the curve and in the order-r subgroup?
  * (No reference counterpart: the reference has g1_is_on_curve, point.cuh:339, as a device helper
  * only and no subgroup test.)  The MSM, scalar_mul and EC-NTT entries assume subgroup members

@@ -88,6 +88,8 @@ EXPORTED = [
     "mbls_fr_coeff_to_extended", "mbls_fr_extended_to_coeff", "mbls_fr_domain_plan",
     "mbls_fr_lookup_multiplicities", "mbls_fr_prefix_sum", "mbls_fr_logup_sum",
     "mbls_fr_inner_products", "mbls_fr_multi_eval", "mbls_fr_powers", "mbls_fr_inner_plan",
+    "mbls_fixed_base_plan", "mbls_fixed_base_recode", "mbls_g1_fixed_base_table", "mbls_g2_fixed_base_table",
+    "mbls_g1_fixed_base_mul", "mbls_g2_fixed_base_mul", "mbls_g1_srs_from_secret",
 ]
 
 _LIB = None
@@ -155,6 +157,10 @@ def lib():
         "mbls_fr_prefix_sum": [P, sz, P, b, P, P, P], "mbls_fr_logup_sum": [P, i32, P, P, sz, P, P, P, P, P],
         "mbls_fr_inner_products": [P, i32, P, i32, sz, P, P], "mbls_fr_multi_eval": [P, i32, sz, P, i32, P, P],
         "mbls_fr_powers": [P, P, sz, P, P], "mbls_fr_inner_plan": [sz, i32, i32, P],
+        "mbls_fixed_base_plan": [i32, P], "mbls_fixed_base_recode": [P, P],
+        "mbls_g1_fixed_base_table": [P, P, P], "mbls_g2_fixed_base_table": [P, P, P],
+        "mbls_g1_fixed_base_mul": [P, P, i32, b, P, P], "mbls_g2_fixed_base_mul": [P, P, i32, b, P, P],
+        "mbls_g1_srs_from_secret": [P, P, i32, i32, P, P],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -962,6 +968,71 @@ def ecntt(points, inverse=False, out=None, stream=None, is_async=False):
     cfg = ntt_config(are_inputs_on_device=_is_dev(points), are_outputs_on_device=_is_dev(out), is_async=is_async,
                      stream=stream)
     check(lib().mbls_g1_ecntt(_p(points), n, 1 if inverse else 0, ctypes.byref(cfg), _p(out)), "mbls_g1_ecntt")
+    return out
+
+
+# ----------------------------------------------------------------------------- fixed base
+FIXED_BASE_PLAN_FIELDS = ("c", "W", "rows", "entries", "entry_bytes", "block", "chunk", "scratch_per_point")
+
+
+def fixed_base_plan(group):
+    """the geometry of the fixed-base multiplication of `group` (mbls_fixed_base_plan; host only):
+    dict of FIXED_BASE_PLAN_FIELDS"""
+    out = (ctypes.c_int64 * len(FIXED_BASE_PLAN_FIELDS))()
+    check(lib().mbls_fixed_base_plan(1 if group == "g1" else 2, out), "mbls_fixed_base_plan")
+    return dict(zip(FIXED_BASE_PLAN_FIELDS, list(out)))
+
+
+def fixed_base_recode(scalar):
+    """the W signed digits of `scalar` mod r (an int below 2^256, standard form), lowest window first,
+    by the function the kernels run (mbls_fixed_base_recode; host only)"""
+    limbs = np.array([(int(scalar) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+    digits = np.zeros(fixed_base_plan("g1")["W"], dtype=np.int32)
+    check(lib().mbls_fixed_base_recode(_p(limbs), _p(digits)), "mbls_fixed_base_recode")
+    return [int(d) for d in digits]
+
+
+def fixed_base_table(group, base, stream=None, is_async=False):
+    """The table of `base` ((12 | 24,) or (1, 12 | 24) uint64 Montgomery affine, numpy or torch) that
+    fixed_base_mul and srs_from_secret take (mbls_g*_fixed_base_table): a device tensor of
+    fixed_base_plan(group)["entries"] affine points, entry w * rows + d - 1 = [d 2^(c w)] base.  The
+    base is assumed to lie in the order-r subgroup."""
+    import torch
+    plan = fixed_base_plan(group)
+    # empty, not zeros: a fill on torch's current stream could land after the build on `stream`
+    table = torch.empty((plan["entries"], plan["entry_bytes"] // 8), dtype=torch.int64, device="cuda")
+    cfg = vec_config(is_a_on_device=_is_dev(base), is_result_on_device=True, stream=stream, is_async=is_async)
+    name = "mbls_g1_fixed_base_table" if group == "g1" else "mbls_g2_fixed_base_table"
+    check(getattr(lib(), name)(_p(base), ctypes.byref(cfg), _p(table)), name)
+    return table
+
+
+def fixed_base_mul(group, table, scalars, *, scalars_mont=False, out=None, stream=None, is_async=False):
+    """out[i] = [scalars[i] mod r] base (mbls_g*_fixed_base_mul) for the base of `table`
+    (fixed_base_table, a device tensor): `scalars` (n, 4) uint64, standard form unless scalars_mont,
+    numpy (host) or torch (device).  Returns (n, 12 | 24) canonical Montgomery affine, identity all
+    zero, host numpy unless `out` is a device tensor.  Not constant time."""
+    n = scalars.shape[0]
+    if out is None:
+        out = np.zeros((n, 12 if group == "g1" else 24), dtype=np.uint64)
+    cfg = vec_config(is_a_on_device=True, is_b_on_device=_is_dev(scalars), is_result_on_device=_is_dev(out),
+                     stream=stream, is_async=is_async)
+    name = "mbls_g1_fixed_base_mul" if group == "g1" else "mbls_g2_fixed_base_mul"
+    check(getattr(lib(), name)(_p(table), _p(scalars), n, bool(scalars_mont), ctypes.byref(cfg), _p(out)), name)
+    return out
+
+
+def srs_from_secret(table, tau, n, lagrange=False, out=None, stream=None, is_async=False):
+    """A KZG SRS of n G1 points from the secret `tau` ((4,) uint64 Montgomery, host numpy) and the
+    table of the generator (mbls_g1_srs_from_secret): out[i] = [tau^i] G, or [L_i(tau)] G over the
+    Fr NTT's domain of size n = 2^k when `lagrange`.  Returns (n, 12) canonical Montgomery affine,
+    host numpy unless `out` is a device tensor.  Not constant time: for unsafe_setup and tests."""
+    if out is None:
+        out = np.zeros((n, 12), dtype=np.uint64)
+    cfg = vec_config(is_a_on_device=True, is_result_on_device=_is_dev(out), stream=stream, is_async=is_async)
+    tau = np.ascontiguousarray(tau, dtype=np.uint64)
+    check(lib().mbls_g1_srs_from_secret(_p(table), _p(tau), n, 1 if lagrange else 0, ctypes.byref(cfg), _p(out)),
+          "mbls_g1_srs_from_secret")
     return out
 
 

@@ -135,7 +135,13 @@ eIcicleError Staging::close(bool is_async) {
 // waits for `done` -- also in case 1: a handle equal to the last one may be a recycled stream (a
 // destroyed ICICLE / torch stream whose address came back) or the default stream after
 // mbls_release_stream, and a wait on an event recorded on the same queue costs HIP nothing.
-// If every context is leased by another thread and the pool is full, wait for a release.
+// If every context is leased by another thread and the pool is full, wait for a release -- unless
+// this thread already holds a lease (an entry that runs other entries of the library, as
+// fixed_base.hip does): such a nested lease never waits, it adds a context past the limit instead.
+// A waiting thread therefore holds no context, every holder can finish, and the pool cannot
+// deadlock, whatever MBLS_SCRATCH_CONTEXTS is and however many threads call in; the pool grows past
+// the limit by at most one context per thread that is nested at the same moment.
+static thread_local int t_leases_held = 0;
 struct Pool {
     std::mutex mu;
     std::condition_variable cv;
@@ -180,7 +186,7 @@ CtxLease::CtxLease(hipStream_t st) : st_(st) {
         if (pick) break;
         if (idle) {
             pick = idle;
-        } else if (v.size() < pool_limit()) {
+        } else if (v.size() < pool_limit() || (!lru && t_leases_held > 0)) {
             std::unique_ptr<StreamCtx> c(new StreamCtx());
             c->device = dev;
             if (hipEventCreateWithFlags(&c->done, hipEventDisableTiming) != hipSuccess) {
@@ -207,10 +213,12 @@ CtxLease::CtxLease(hipStream_t st) : st_(st) {
         return;
     }
     ctx_ = pick;
+    ++t_leases_held;  // a lease is taken and given back by one thread (RAII inside one call)
 }
 
 CtxLease::~CtxLease() {
     if (!ctx_) return;
+    --t_leases_held;
     // everything the call enqueued is ordered before `done`.  A call that forked work to the
     // side streams joins them back before it returns; an early error return may not have, so
     // the side streams' tails are joined here whenever the call forked (a join event each)
