@@ -71,26 +71,44 @@ struct F28 {
 // Montgomery product (a b + m p) / 2^392, product scanning; column k accumulates its
 // a_i b_(k-i) and m_i p_(k-i) in ONE 64-bit register as one v_mad_u64_u32 chain (mbls_madchain.hpp:
 // written as C++ additions LLVM gave every column a fresh chain plus a 64-bit merge add, ~39
-// extra instructions per product).  Columns by compile-time recursion; SQ: the square's column
-// (cross products against the doubled operand d, then the diagonal term); C2/D2: mul2's second
-// product.
+// extra instructions per product).  Columns by compile-time recursion; the square's column is the
+// cross products against the doubled operand d, then the diagonal term; mul2 / mul4 append their
+// further products to the same column.
+//
+// A column is the chain  [m_(k-1) P_0, >> 28]  products  reduction terms  in as few asm statements
+// as it has terms for (mbls_madchain.hpp: every statement boundary on the chain costs a lone wave a
+// wait state), then m_k = (lo NINV) & MASK (k < NL) or the output limb (k >= NL) in C++.  The m_k P_0
+// step that clears the low 28 bits, and the shift behind it, open the NEXT column's statement:
+// they need m_k, which needs this statement's result, so they cannot close this one.
 template <int K>
-MBLS_DEV void reduce_col(uint64_t& acc, uint32_t (&m)[NL], F28& r) {
-    constexpr int LO = K > NL - 1 ? K - (NL - 1) : 0;
-    madc::col<K, LO, (K < NL ? K : NL) - 1, true>(acc, m, P);
+constexpr int col_lo() { return K > NL - 1 ? K - (NL - 1) : 0; }
+template <int K>
+constexpr int col_n() { return (K < NL - 1 ? K : NL - 1) - col_lo<K>() + 1; }  // products of one a b in column K
+
+// column K over the NV product terms va[i] vb[i]
+template <int K, int NV>
+MBLS_DEV void run_col(uint64_t& acc, uint32_t (&m)[NL], F28& r, const uint32_t* va, const uint32_t* vb) {
+    constexpr int LO = col_lo<K>(), NR = (K < NL ? K : NL) - LO;
+    uint32_t sa[NR > 0 ? NR : 1], sb[NR > 0 ? NR : 1];
+    madc::fill<K, LO, LO + NR - 1>(sa, sb, m, P);
+    if constexpr (K > 0 && K <= NL)
+        madc::chain<true, 28, NV, NR>(acc, m[K - 1], P[0], va, vb, sa, sb);  // column K - 1's low 28 bits become zero
+    else
+        madc::chain<false, 28, NV, NR>(acc, 0u, 0u, va, vb, sa, sb);
     if constexpr (K < NL) {
         m[K] = ((uint32_t)acc * NINV) & MASK;
-        madc::mad1<true>(acc, m[K], P[0]);  // the low 28 bits become zero
     } else {
         r.l[K - NL] = (uint32_t)acc & MASK;
+        acc >>= 28;
     }
-    acc >>= 28;
 }
 template <int K>
 MBLS_DEV void mul_cols(uint64_t& acc, uint32_t (&m)[NL], F28& r, const F28& a, const F28& b) {
     if constexpr (K < 2 * NL - 1) {
-        madc::col<K, (K > NL - 1 ? K - (NL - 1) : 0), (K < NL - 1 ? K : NL - 1), false>(acc, a.l, b.l);
-        reduce_col<K>(acc, m, r);
+        constexpr int LO = col_lo<K>(), N = col_n<K>();
+        uint32_t va[N], vb[N];
+        madc::fill<K, LO, LO + N - 1>(va, vb, a.l, b.l);
+        run_col<K, N>(acc, m, r, va, vb);
         mul_cols<K + 1>(acc, m, r, a, b);
     }
 }
@@ -98,10 +116,11 @@ template <int K>
 MBLS_DEV void mul2_cols(uint64_t& acc, uint32_t (&m)[NL], F28& r, const F28& a, const F28& b, const F28& c,
                         const F28& d) {
     if constexpr (K < 2 * NL - 1) {
-        constexpr int LO = K > NL - 1 ? K - (NL - 1) : 0, HI = K < NL - 1 ? K : NL - 1;
-        madc::col<K, LO, HI, false>(acc, a.l, b.l);
-        madc::col<K, LO, HI, false>(acc, c.l, d.l);
-        reduce_col<K>(acc, m, r);
+        constexpr int LO = col_lo<K>(), N = col_n<K>();
+        uint32_t va[2 * N], vb[2 * N];
+        madc::fill<K, LO, LO + N - 1>(va, vb, a.l, b.l);
+        madc::fill<K, LO, LO + N - 1>(va + N, vb + N, c.l, d.l);
+        run_col<K, 2 * N>(acc, m, r, va, vb);
         mul2_cols<K + 1>(acc, m, r, a, b, c, d);
     }
 }
@@ -109,22 +128,24 @@ MBLS_DEV void mul2_cols(uint64_t& acc, uint32_t (&m)[NL], F28& r, const F28& a, 
 template <int K>
 MBLS_DEV void mul4_cols(uint64_t& acc, uint32_t (&m)[NL], F28& r, const F28 (&x)[8]) {
     if constexpr (K < 2 * NL - 1) {
-        constexpr int LO = K > NL - 1 ? K - (NL - 1) : 0, HI = K < NL - 1 ? K : NL - 1;
-        madc::col<K, LO, HI, false>(acc, x[0].l, x[1].l);
-        madc::col<K, LO, HI, false>(acc, x[2].l, x[3].l);
-        madc::col<K, LO, HI, false>(acc, x[4].l, x[5].l);
-        madc::col<K, LO, HI, false>(acc, x[6].l, x[7].l);
-        reduce_col<K>(acc, m, r);
+        constexpr int LO = col_lo<K>(), N = col_n<K>();
+        uint32_t va[4 * N], vb[4 * N];
+        madc::fill<K, LO, LO + N - 1>(va, vb, x[0].l, x[1].l);
+        madc::fill<K, LO, LO + N - 1>(va + N, vb + N, x[2].l, x[3].l);
+        madc::fill<K, LO, LO + N - 1>(va + 2 * N, vb + 2 * N, x[4].l, x[5].l);
+        madc::fill<K, LO, LO + N - 1>(va + 3 * N, vb + 3 * N, x[6].l, x[7].l);
+        run_col<K, 4 * N>(acc, m, r, va, vb);
         mul4_cols<K + 1>(acc, m, r, x);
     }
 }
 template <int K>
 MBLS_DEV void sqr_cols(uint64_t& acc, uint32_t (&m)[NL], F28& r, const F28& a, const uint32_t (&d)[NL]) {
     if constexpr (K < 2 * NL - 1) {
-        constexpr int LO = K > NL - 1 ? K - (NL - 1) : 0;
-        madc::col<K, LO, (K + 1) / 2 - 1, false>(acc, a.l, d);  // i < k - i: a_i (2 a_(k-i)) (none at k = 0)
-        if constexpr ((K & 1) == 0) madc::mad1<false>(acc, a.l[K >> 1], a.l[K >> 1]);
-        reduce_col<K>(acc, m, r);
+        constexpr int LO = col_lo<K>(), NC = (K + 1) / 2 - LO, N = NC + ((K & 1) == 0 ? 1 : 0);
+        uint32_t va[N], vb[N];
+        madc::fill<K, LO, LO + NC - 1>(va, vb, a.l, d);  // i < k - i: a_i (2 a_(k-i)) (none at k = 0)
+        if constexpr ((K & 1) == 0) va[NC] = vb[NC] = a.l[K >> 1];
+        run_col<K, N>(acc, m, r, va, vb);
         sqr_cols<K + 1>(acc, m, r, a, d);
     }
 }
